@@ -1364,15 +1364,22 @@ __device__ __forceinline__ float poisson_draw(float lam, float u, float zn) {
     while (u > c && k < 200) {
       k++;
       p *= lam / (float)k;
-      c += p;
+      const float cn = c + p;
+      if (cn == c) break;     // the sum has stopped growing below u: the tail is exhausted (see below)
+      c = cn;
     }
 #else
     float p = __expf(-lam), c = p;
     int k = 0;
+    // the fp32 cumulative sum levels off a few ulps below 1 (0.9999999 for lam = 1) while u01 reaches 1.0: for a u
+    // above that level `u > c` never fails and the count would run to the cap (200 photons in a dark pixel, ~1e-7 of
+    // the pixels, at different u on the two sides).  Stop where the sum stops growing: the count there is the tail's end
     while (u > c && k < 200) {
       k++;
       p *= lam * __builtin_amdgcn_rcpf((float)k);
-      c += p;
+      const float cn = c + p;
+      if (cn == c) break;
+      c = cn;
     }
 #endif
     return (float)k;

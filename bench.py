@@ -17,6 +17,14 @@ independent, so N GPUs run N x 256 seeds with no data-path collective (weak scal
 collectives are the MAX over ranks of the timed region and one all_gather of per-environment
 returns in the epilogue.
 
+A plain run does what `value` needs: set-up, the reset and the untimed steps in front of the timed region, the K
+timed steps and, with the reset prefetch on, the measured whole episode behind them whose reset `value` amortises.
+`--full` adds every other figure below (the plain-order and integrator-only passes, `roofline.alone`, the stage split,
+`fast_mode`, `configs`, `sac_update`, `episode_end_to_end`, the denoiser launch alone, `cpu_baseline`).
+`--dump-outputs DIR` writes what the last timed step returned (actions, states, rewards) and the Strehl ratios it left
+as DIR/<name>.npy: with the same arguments the inputs are the same from run to run, so two builds compare output for
+output.
+
 What the ONE JSON line (rank 0) says:
   value            env steps/s with the metric's episode structure: one env.reset() per
                    `--episode-len` (1000) frames, timed in this run, amortised into the K timed steps:
@@ -121,6 +129,13 @@ def parse_args():
                          "the loop does not stay closed) instead of SURVEY 8(d)'s policy (Xavier, seed 1234, last layer zero)")
     ap.add_argument("--no-episode-end-to-end", action="store_true",
                     help="skip the measured training episode (reset + episode_len steps + episode_len SAC updates)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure as well: the plain-order and integrator-only passes, the "
+                         "stage split, the fast mode, the side configurations, the SAC update, the training episode, the "
+                         "denoiser launch alone and the CPU baseline.  Without it a run does only what `value` needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (actions, states, per-agent rewards) and the Strehl "
+                         "ratios it left as DIR/<name>.npy (float32, rank 0's environments)")
     return ap.parse_args()
 
 
@@ -402,7 +417,7 @@ class Workload(object):
     def one_step(self):
         # choose_action + env_step as ONE library call (aomarl_policy_env_step): the launches of policy.select_action
         # followed by env.step, one host round trip
-        _, self.state, self.last_r, _, _ = self.env.policy_step(self.policy, self.state)
+        self.last_a, self.state, self.last_r, _, _ = self.env.policy_step(self.policy, self.state)
 
     def one_step_integrator(self):
         # TrainerRPC.env_step(a=None, linear_control=True): the integrator alone (train_rpc.py:577-578)
@@ -719,6 +734,7 @@ def main():
     # a moment ago has not run yet -- all of them -- are run by this call: the same figure)
     reset_open_s = w.time_reset(dist, backend)
     elapsed, t_enq, fk_ms = w.timed(args.steps, args.warmup, dist, backend, settle=args.settle)
+    outputs = last_step_outputs(w) if args.dump_outputs and rank == 0 else None
     envs_total = args.envs * world
     transient_s = w.transient_excess(args.steps, elapsed)
     # What a reset costs an episode: in the open, all of it; prefetched, the timed steps already carry their share
@@ -747,9 +763,10 @@ def main():
         shards = got
 
     pipe_state = sim.frame_pipeline_state()
-    # one whole episode, measured (reset + episode_len steps): what `value` amortises, without the amortisation
+    # one whole episode, measured (reset + episode_len steps): what `value` amortises, without the amortisation (without
+    # --full only with the reset prefetch on: `value` then takes the reset's cost from it)
     whole = None
-    if not args.timed_only and not args.no_whole_episode:
+    if not args.timed_only and not args.no_whole_episode and (rp_on or args.full):
         if rp_on:
             w.time_episode(args.episode_len, dist, backend)      # (an episode whose prefetch runs to its end)
         ep_s, rs = w.time_episode(args.episode_len, dist, backend, split_reset=True)
@@ -766,8 +783,8 @@ def main():
     # the same steps in the plain call order (frame kernel alone on the GPU, the chains behind it): what the
     # pipeline buys, and the frame kernel's duration without the chains' kernels beside it
     plain = None
-    do_plain = bool(pipe_state[0])
-    if dist is not None:                    # a collective decision: the pass has barriers inside (ranks probe their own
+    do_plain = bool(pipe_state[0]) and args.full
+    if dist is not None and args.full:      # a collective decision: the pass has barriers inside (ranks probe their own
         t = torch.tensor([int(do_plain)], dtype=torch.int32,      # call order and may differ)
                          device=device if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -785,7 +802,7 @@ def main():
     # its normalisation runs), plain call order (the call-by-call step), from a reset: a closed loop's Strehl beside
     # the policy's
     integ = None
-    if not args.timed_only and denoiser is None:
+    if args.full and not args.timed_only and denoiser is None:
         if pipe_state[0]:
             sim.set_option("frame_pipeline", 0)
         try:
@@ -807,7 +824,7 @@ def main():
                 sim.set_option("frame_pipeline", 1)
     # side figure: the same whole episode with the NEXT reset's rounds hidden beside it (single-GPU runs)
     rp_side = None
-    if whole is not None and not rp_on and dist is None and not args.no_prefetch:
+    if args.full and whole is not None and not rp_on and dist is None and not args.no_prefetch:
         try:
             env.supervisor.reset_prefetch = "same"
             w.time_episode(args.episode_len)             # (begins the prefetch, runs it to its end)
@@ -821,7 +838,7 @@ def main():
     # when the timed steps left a pipelined frame in flight)
     if pipe_state[0] and args.timed_only:
         w.reset()
-    stage_diag = None if args.timed_only else stage_split(w, min(20, args.steps))
+    stage_diag = stage_split(w, min(20, args.steps)) if args.full and not args.timed_only else None
 
     out = None
     if rank == 0:
@@ -887,8 +904,8 @@ def main():
     if dist is not None:
         dist.barrier()
 
-    # ---- everything below is single-GPU side information (rank 0 of an N = 1 run)
-    if rank == 0 and world == 1:
+    # ---- everything below is single-GPU side information (rank 0 of an N = 1 run with --full)
+    if rank == 0 and world == 1 and args.full:
         main_is_headline = args.config == WORKLOAD and not denoiser
         if denoiser:
             out["denoiser_kernel"] = denoiser_roofline(w, args.precision == "f32")
@@ -944,10 +961,40 @@ def main():
         out["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(s_main)
     elif rank == 0:
         out["cpu_baseline"] = None
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def last_step_outputs(w):
+    """What the last timed step handed its caller -- the sampled actions, the next states, the per-agent rewards --
+    and the Strehl ratios it left (HipSim.strehl, short and long exposure), copied to the host (float32, one row per
+    environment)."""
+    import numpy as np
+    got = {"actions": w.last_a, "states": w.state, "rewards": w.last_r, "strehl": w.sim.strehl}
+    return {k: np.ascontiguousarray(v.detach().float().cpu().numpy()) for k, v in got.items()}
+
+
+def write_outputs(dirname, outputs):
+    """DIR/<name>.npy for every output.  Beyond DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of environments
+    (rows) of every array, its indices in env_index.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = next(iter(outputs.values())).shape[0]
+        keep = max(1, n * (DUMP_LIMIT_BYTES - 8 * n) // total)
+        idx = np.sort(np.random.default_rng(1234).choice(n, keep, replace=False))
+        outputs = {k: a[idx] for k, a in outputs.items()}
+        outputs["env_index"] = idx.astype(np.float64)
+    for name, a in outputs.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def stage_split(w, steps):

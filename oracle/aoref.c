@@ -232,7 +232,9 @@ void aoref_sh_image(const float *phase, const float *mpupil, int nvalid, int pdi
 }
 
 /* Poisson sample with mean lam from uniform/normal draws: inversion for lam < 30, rounded normal
- * approximation above (the product uses the identical rule). */
+ * approximation above (the product uses the identical rule).  The fp32 cumulative sum levels off a
+ * few ulps below 1 while u can reach 1.0: the inversion stops where the sum stops growing instead of
+ * running to the cap of 200. */
 static float poisson_draw(float lam, float u, float zn) {
   if (!(lam > 0.f)) return 0.f;
   if (lam < 30.f) {
@@ -241,7 +243,9 @@ static float poisson_draw(float lam, float u, float zn) {
     while (u > c && k < 200) {
       k++;
       p *= lam / (float)k;
-      c += p;
+      const float cn = c + p;
+      if (cn == c) break;
+      c = cn;
     }
     return (float)k;
   }

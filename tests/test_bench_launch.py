@@ -128,6 +128,61 @@ def test_amortised_rate():
     assert abs(v - 256 * 100 / (0.07 + 0.1 * 0.02)) < 1e-6
 
 
+def test_dumped_outputs_stay_within_the_limit(tmp_path):
+    """--dump-outputs: every array as <name>.npy; beyond the limit the same seeded sample of environments (rows) of
+    every array, the same sample every run."""
+    import numpy as np
+    import bench
+    small = {"states": np.arange(12, dtype=np.float32).reshape(4, 3), "rewards": np.ones((4, 2), dtype=np.float32)}
+    bench.write_outputs(str(tmp_path / "small"), small)
+    assert sorted(os.listdir(tmp_path / "small")) == ["rewards.npy", "states.npy"]
+    assert np.array_equal(np.load(tmp_path / "small" / "states.npy"), small["states"])
+    n = 4096
+    big = {"states": np.random.rand(n, 5000).astype(np.float32), "rewards": np.random.rand(n, 14).astype(np.float32)}
+    for d in ("big1", "big2"):
+        bench.write_outputs(str(tmp_path / d), big)
+    got = {f: np.load(tmp_path / "big1" / f) for f in os.listdir(tmp_path / "big1")}
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_LIMIT_BYTES
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    idx = got["env_index.npy"].astype(np.int64)
+    assert 0 < idx.size < n and np.array_equal(got["states.npy"], big["states"][idx])
+    assert np.array_equal(got["rewards.npy"], big["rewards"][idx])
+    assert np.array_equal(np.load(tmp_path / "big2" / "env_index.npy"), got["env_index.npy"])
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run: the headline figure only (no side pass), exactly --steps timed steps, and --dump-outputs writes
+    what the last timed step returned -- the same arrays, bit for bit, in a second run with the same arguments."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "AOMARL_DIST_FORCE"):
+        env.pop(k, None)
+    outs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
+               "--envs", "8", "--config", "production_sh_10x10_2m", "--episode-len", "50",
+               "--dump-outputs", str(tmp_path / run)]
+        p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        outs.append(json.loads(lines[0]))
+    out = outs[0]
+    assert out["steps"] == 6 and out["warmup"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert abs(out["ms_per_step"] - 8 / out["value"] * 1e3) < 1e-9 * out["ms_per_step"]
+    assert sum(out["launched"].get(k, 0) for k in out["launched"] if k.startswith("actor:")) == 6
+    for k in ("configs", "fast_mode", "sac_update", "episode_end_to_end"):
+        assert k not in out
+    assert out["cpu_baseline"] is None and out["stage_ms"] is None and out["integrator_only"] is None
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["actions.npy", "rewards.npy", "states.npy", "strehl.npy"]
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and a.shape[0] == 8 and np.isfinite(a).all()
+        assert np.array_equal(a, b), f
+
+
 @pytest.mark.gpu
 def test_two_rank_bench_on_one_gpu():
     env = dict(os.environ, AOMARL_DIST_BACKEND="gloo")

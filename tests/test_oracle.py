@@ -27,6 +27,18 @@ def test_philox_known_answers():
     assert not np.array_equal(aoref.normals(7, 0, 4, 16), aoref.normals(7, 0, 3, 16))
 
 
+def test_photon_noise_inversion_stops_at_the_end_of_the_tail():
+    """The Poisson inversion below a mean of 30 sums the probabilities in fp32; the sum levels off a few ulps below 1
+    while the uniform can reach 1.0.  A uniform above that level must end the count where the sum stops growing, not
+    at the loop's cap: these 2^24 means and noise streams hold one such draw (mean 22.9, 200 photons before)."""
+    L = aoref.lib()
+    lam = np.random.default_rng(0).uniform(0.05, 29.9, 1 << 24).astype(np.float32)
+    cube = lam.copy()
+    L.aoref_sh_noise(cube, cube.size // 64, 64, 0.0, 31, 3)
+    assert cube.max() < 80, (cube.max(), lam[np.argmax(cube)])
+    assert abs(float(cube.mean()) / float(lam.mean()) - 1) < 1e-3
+
+
 def _np_extrude_plus_x(p, A, B, ist, amp, eps):
     """iterkolmo.py:278-286 in NumPy."""
     n = p.shape[0]
