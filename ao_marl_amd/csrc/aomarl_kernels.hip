@@ -2448,12 +2448,12 @@ __global__ __launch_bounds__(256) void k_wfs_spot_fast(DevSys sys, DevState st, 
 #define FW_LIT 0x10000
 #define FW_FULL 0x20000
 #define FW_SUB 0x40000
-// science-path phase in revolutions for v_sin / v_cos.  The instructions reduce their argument
-// themselves for |x| <= 256 revolutions (ISA: valid input domain [-256, 256], 0 outside); the
-// science wavelength sees |phase| / lambda of a few tens at most (an 8 m pupil at r0 = 0.16 m has
-// 2 um rms of optical path, 1.65 um wavelength: 422 um would be needed to leave the domain), so
-// the explicit round-and-subtract the WFS path keeps (its fused multiply-subtract also saves one
-// rounding, which the 2e-5 image tolerance needs) is dropped here.
+// science-path phase in revolutions for v_sin / v_cos, unreduced.  The ISA text gives the instructions a
+// valid input domain of [-256, 256] revolutions; measured on gfx950 (tests/test_gpu_phase_range.py), they
+// reduce far past it: phases of +-660 um (1320 sensor / 400 science revolutions) give the slopes, spots
+// and Strehl ratios of the same frame without the whole-period offset to fp32 round-off of the phase
+// itself.  The explicit round-and-subtract the WFS path keeps (its fused multiply-subtract saves one
+// rounding, which the 2e-5 image tolerance needs) is therefore dropped here.
 __device__ __forceinline__ float sci_rev(float ph, float inv_lambda) { return ph * inv_lambda; }
 
 // Uniform tables that nothing writes during a launch, read through the CONSTANT address space: the compiler
@@ -2791,8 +2791,8 @@ void k_frame_wave(DevSys sys, DevState st, int env_begin,
         const f32x2 b01 = pk_mul_s(p01, til2), b23 = pk_mul_s(p23, til2);
         if constexpr (QF) {
           // Slopes only: the sensor's phase goes to v_sin / v_cos as it stands, in revolutions, like the science
-          // path's (the instructions reduce |x| <= 256 themselves; an 8 m pupil sees a few tens of revolutions at
-          // 0.5 um).  The explicit round-and-subtract below keeps one rounding less in the REDUCED argument -- what
+          // path's (the instructions reduce the argument themselves, also past the ISA's +-256: see sci_rev; an 8 m
+          // pupil sees a few tens of revolutions at 0.5 um).  The explicit round-and-subtract below keeps one rounding less in the REDUCED argument -- what
           // the 2e-5 image tolerance of the image-producing instantiations needs; the centre of gravity does not see
           // it (6e-8 x |revolutions| of phase per pixel, unbiased: 1e-7 pixel of centroid), and the reference itself
           // takes cos / sin of the unreduced float phase.  Six vector instructions less per tile.

@@ -59,3 +59,33 @@ def calibrated_hip(name, nfilt=5, hw=8):
     cal = modal.calibrate(s, sysm, lambda: HipSim(s, nenv=512, keep_phase=True), nfilt=nfilt,
                           backend_id=HipSim.calibration_id())
     return sysm, s, cal
+
+
+class QuickOracle(aoref.OracleSim):
+    """Oracle env whose reset only runs a few extrusions (a full 40x40 refresh is 3888 GEMVs)."""
+    NEXT = 40
+
+    def reset(self, seed):
+        s = self.s
+        self.seed, self.frame = int(seed), 0
+        self.accumx = np.zeros(s.nscreens, dtype=np.float32)
+        self.accumy = np.zeros(s.nscreens, dtype=np.float32)
+        self.ext_count = [0] * s.nscreens
+        for l in range(s.nscreens):
+            self.screens[l][:] = 0
+            for _ in range(self.NEXT):
+                self._extrude(l, 1 if s.deltax[l] > 0 else -1)
+        self._alloc_ctrl()
+        for sh in self.dm_shapes:
+            sh[:] = 0
+        self.reset_strehl()
+        self.raytrace_target()
+
+
+def push_screens(sim, oracles):
+    """Copy the oracles' screens and extrusion counters into the HIP state (ring origin 0)."""
+    s = sim.s
+    for l, d in enumerate(s.screen_dim):
+        sim.set_screen(l, np.stack([o.screens[l] for o in oracles]))
+        for e, o in enumerate(oracles):
+            sim.t["ext_count"][e, l] = o.ext_count[l]

@@ -8,7 +8,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from ao_marl_amd import geometry as G, modal, params, system  # noqa: E402
-from oracle import aoref  # noqa: E402
+from tests import helpers  # noqa: E402
 
 L_NAME = "production_sh_40x40_8m_3layers"
 
@@ -24,33 +24,8 @@ def large():
     return sysm, s, cal
 
 
-class QuickOracle(aoref.OracleSim):
-    """Oracle env whose reset only runs a few extrusions (a full 40x40 refresh is 3888 GEMVs)."""
-    NEXT = 40
-
-    def reset(self, seed):
-        s = self.s
-        self.seed, self.frame = int(seed), 0
-        self.accumx = np.zeros(s.nscreens, dtype=np.float32)
-        self.accumy = np.zeros(s.nscreens, dtype=np.float32)
-        self.ext_count = [0] * s.nscreens
-        for l in range(s.nscreens):
-            self.screens[l][:] = 0
-            for _ in range(self.NEXT):
-                self._extrude(l, 1 if s.deltax[l] > 0 else -1)
-        self._alloc_ctrl()
-        for sh in self.dm_shapes:
-            sh[:] = 0
-        self.reset_strehl()
-        self.raytrace_target()
-
-
-def _push(sim, oracles):
-    s = sim.s
-    for l, d in enumerate(s.screen_dim):
-        sim.set_screen(l, np.stack([o.screens[l] for o in oracles]))
-        for e, o in enumerate(oracles):
-            sim.t["ext_count"][e, l] = o.ext_count[l]
+QuickOracle = helpers.QuickOracle
+_push = helpers.push_screens
 
 
 # (unfused, write_bincube, precision).  unfused 0: one-pass frame kernel (science + WFS from the same
