@@ -1766,7 +1766,7 @@ __device__ __forceinline__ void spot_cog_f32_pk(const DevSys &sys, const DevStat
 
 // ---------------------------------------------------------------------------------------------
 // Slopes only, fp32, WITHOUT the spot: the three moments of the binned image as quadratic forms of the
-// pupil field (28 matrix instructions per sub-aperture instead of 48, 8 packed vector instructions instead of 32).
+// pupil field (24 matrix instructions per sub-aperture -- six 16 x 16 x 16 products -- instead of the transform's 48).
 //
 // The binned image covers the central 32 x 32 frequencies f = +-(j + 1/2), j = 0 .. 15 of the half-pixel-shifted
 // 64-point transform, every one of them exactly once (npix * nrebin = 32), and the pixel coordinate of a frequency
@@ -1779,13 +1779,20 @@ __device__ __forceinline__ void spot_cog_f32_pk(const DevSys &sys, const DevStat
 //     sum I           = < M, Er M Er^T + Ei M Ei^T >
 //     sum (X - 7.5) I =  2 < M, Ei S Er^T >
 //     sum (Y - 7.5) I =  2 < S, Ei M Er^T >            (< A, B > = sum_{y', y} A[y'][y] B[y'][y])
+// The first and the third share ONE accumulator.  G1 = Er M Er^T + Ei M Ei^T is symmetric, and with G2 = Ei M Er^T
+//     X = (Er + Ei) M Er^T + (Ei - Er) M Ei^T = G1 + (G2 - G2^T):
+// the antisymmetric part drops out against the symmetric M, the symmetric part against the antisymmetric S, and
+// < S, G2 - G2^T > = 2 < S, G2 >, so that
+//     sum I = < M, X >,      sum (Y - 7.5) I = < S, X >
+// and G2 is never formed (tests/test_qf_six_products.py; same float32 error as the seven-product form).
 // -- the same numbers as transform, |.|^2, 2 x 2 binning and centre of gravity, to fp32 round-off (2e-7 pixels
 // against the 64 x 64 FFT in float64, tools/qf_cog_check.py).  Not usable with noise or when the image is wanted.
 //
 // On the matrix cores: lane (q, c) holds E[y = c][x = 4q + s], which is the A operand of a product E . (..) AND
 // the B operand of a product (..) . E^T:  W = M Er^T, M Ei^T, S Er^T  (A = the constant [x' = c][x = 4q + s], 12
-// instructions) come out as [x' = 4q + r][y = c], the B operand of  Er W, Ei W  (16 instructions), whose results
-// [y' = 4q + r][y = c] meet the same constants again (M symmetric, S antisymmetric) in 8 packed multiply-adds.
+// instructions) come out as [x' = 4q + r][y = c], the B operand of  (Er + Ei) W, (Ei - Er) W, Ei W  (12 instructions),
+// whose results [y' = 4q + r][y = c] meet the same constants again (M symmetric, S antisymmetric) in 6 packed
+// multiply-adds.
 struct SpotQf { f32x2 Ml, Mh, Sl, Sh; };          // M[c][4q + s], S[c - (4q + s)], s = 0 .. 3
 
 __device__ __forceinline__ SpotQf spot_qf_consts(int lane, const float2 *sTw /* [128]: cos, sin(2 pi k / 128) */) {
@@ -1828,14 +1835,24 @@ __global__ __launch_bounds__(128) void k_fill_qf_tab(float *__restrict__ tab) {
   }
 }
 
-// The three moments of one sub-aperture, summed over the wave: returns z with  row 0 (lanes 0 .. 15): sum I,
-// row 1: sum (Y - 7.5) I / 2 (sign: see qf_slopes),  row 2: sum (X - 7.5) I / 2  -- every lane of a row holds the total.
+// The three moments of one sub-aperture, summed over the wave: returns z with  row 0 (lanes 0 .. 15): sum I = < M, X >,
+// row 1: -sum (Y - 7.5) I = < S, X > in the result layout (sign and the factors: see qf_slopes),  row 2: sum (X - 7.5) I / 2
+// = < M, G3 >  -- every lane of a row holds the total.
 // Round 6: 10 cross-lane instructions instead of 3 x 7 (tools/permlanebench.hip): gfx950's row swaps fold the four
 // 16-lane rows of TWO registers into one (v_permlane32_swap: the upper half of the first operand against the lower
 // half of the second -- [a_lo | b_lo] + [a_hi | b_hi]; v_permlane16_swap: the odd rows of the first against the even
 // rows of the second), so that one register carries all three sums through the four in-row DPP steps; and the two
-// products that make sum I share an accumulator (two packed instructions less).
+// products that make X share an accumulator (two packed instructions less).
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+// A/B switches (make variant): A = Er + Ei, B = Ei - Er as four packed additions behind stage 1 (1) or as eight plain
+// ones the compiler spreads over stage 2 (0); X on one accumulator (0) or on two summed by two packed additions (1:
+// with packed A, B that is 114 registers, past the 112 three waves per SIMD beside a product's workgroup leave)
+#ifndef FW_QF6_PK
+#define FW_QF6_PK 1
+#endif
+#ifndef FW_QF6_ACC2
+#define FW_QF6_ACC2 0
+#endif
 __device__ __forceinline__ float swap32_add(float a, float b) {
   const u32x2 t = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
   return __uint_as_float(t[0]) + __uint_as_float(t[1]);      // rows 0, 1: a (rows 0 + 2, 1 + 3); rows 2, 3: b
@@ -1853,22 +1870,47 @@ __device__ __forceinline__ float spot_qf_moments(const SpotQf &K, const float (&
     Wi = mfma16(Mc[s], ei[s], Wi);               // (M Ei^T)[x'][y]
     V = mfma16(Sc[s], er[s], V);                 // (S Er^T)[x'][y]
   }
-  f32x4 G1 = z4, G2 = z4, G3 = z4;
+  // A = Er + Ei, B = Ei - Er (er is dead from here)
+#if FW_QF6_PK
+  const f32x2 er01 = {er[0], er[1]}, er23 = {er[2], er[3]}, ei01 = {ei[0], ei[1]}, ei23 = {ei[2], ei[3]};
+  __builtin_amdgcn_sched_barrier(0);             // (behind stage 1: the cos / sin that made er, ei are long done)
+  const f32x2 a01 = pk_add(er01, ei01), a23 = pk_add(er23, ei23);
+  const f32x2 b01 = pk_sub(ei01, er01), b23 = pk_sub(ei23, er23);
+  PK_END_TO_MFMA();
+  const float A[4] = {a01.x, a01.y, a23.x, a23.y}, B[4] = {b01.x, b01.y, b23.x, b23.y};
+#else
+  float A[4], B[4];
+#pragma unroll
+  for (int s = 0; s < 4; s++) { A[s] = er[s] + ei[s]; B[s] = ei[s] - er[s]; }
+#endif
+#if FW_QF6_ACC2
+  f32x4 Xa = z4, Xb = z4, G3 = z4;
 #pragma unroll
   for (int s = 0; s < 4; s++) {
-    G1 = mfma16(er[s], Wr[s], G1);               // (Er M Er^T + Ei M Ei^T)[y'][y]: both products into one accumulator
-    G2 = mfma16(ei[s], Wr[s], G2);               // (Ei M Er^T)[y'][y]
+    Xa = mfma16(A[s], Wr[s], Xa);                // ((Er + Ei) M Er^T)[y'][y]
+    Xb = mfma16(B[s], Wi[s], Xb);                // ((Ei - Er) M Ei^T)[y'][y]
     G3 = mfma16(ei[s], V[s], G3);                // (Ei S Er^T)[y'][y]
-    G1 = mfma16(ei[s], Wi[s], G1);
   }
-  // constants in the result layout: M[4q + r][c] = M[c][4q + r] = Mc[r];  S[(4q + r) - c] = -Sc[r]
   PK_GUARD_MFMA();
-  f32x2 p0 = pk_mul(pk_lo(G1), K.Ml);
+  const f32x2 Xl = pk_add(pk_lo(Xa), pk_lo(Xb)), Xh = pk_add(pk_hi(Xa), pk_hi(Xb));
+#else
+  f32x4 X = z4, G3 = z4;
+#pragma unroll
+  for (int s = 0; s < 4; s++) {
+    X = mfma16(A[s], Wr[s], X);                  // ((Er + Ei) M Er^T + (Ei - Er) M Ei^T)[y'][y]: one accumulator
+    G3 = mfma16(ei[s], V[s], G3);                // (Ei S Er^T)[y'][y]
+    X = mfma16(B[s], Wi[s], X);
+  }
+  PK_GUARD_MFMA();
+  const f32x2 Xl = pk_lo(X), Xh = pk_hi(X);
+#endif
+  // constants in the result layout: M[4q + r][c] = M[c][4q + r] = Mc[r];  S[(4q + r) - c] = -Sc[r]
+  f32x2 p0 = pk_mul(Xl, K.Ml);
   f32x2 px = pk_mul(pk_lo(G3), K.Ml);
-  f32x2 py = pk_mul(pk_lo(G2), K.Sl);
-  pk_acc_fma(p0, pk_hi(G1), K.Mh);
+  f32x2 py = pk_mul(Xl, K.Sl);
+  pk_acc_fma(p0, Xh, K.Mh);
   pk_acc_fma(px, pk_hi(G3), K.Mh);
-  pk_acc_fma(py, pk_hi(G2), K.Sh);
+  pk_acc_fma(py, Xh, K.Sh);
   const float s0 = p0.x + p0.y, tx = px.x + px.y, ty = py.x + py.y;
   // (the second operand of the second fold is a register that is dead by now: rows 2, 3 of that fold -- row 3 of z --
   // are never read, and a swap of ty with itself would need a copy first)
@@ -1879,12 +1921,12 @@ __device__ __forceinline__ float spot_qf_moments(const SpotQf &K, const float (&
   z += dpp_f<0x140>(z);     // row_mirror -> every lane holds its 16-lane row sum
   return z;
 }
-// the two slopes of a sub-aperture from its moments (sum I, sum (X - 7.5) I / 2, -sum (Y - 7.5) I / 2 as
-// spot_qf_moments leaves them)
+// the two slopes of a sub-aperture from its moments (sum I, sum (X - 7.5) I / 2, -sum (Y - 7.5) I as
+// spot_qf_moments leaves them: the y moment comes whole out of the shared accumulator, the x moment halved)
 __device__ __forceinline__ void qf_slopes(const DevSys &sys, float s0, float tx, float ty, float &sx, float &sy) {
   if (s0 > 0.f) {
-    const float inv = 2.f * __builtin_amdgcn_rcpf(s0);  // 1 ulp; slopes are compared at 1e-4"
-    sx = (fmaf(tx, inv, 7.5f) - sys.cog_offset) * sys.cog_scale;
+    const float inv = __builtin_amdgcn_rcpf(s0);        // 1 ulp; slopes are compared at 1e-4"
+    sx = (fmaf(tx, 2.f * inv, 7.5f) - sys.cog_offset) * sys.cog_scale;
     sy = (fmaf(-ty, inv, 7.5f) - sys.cog_offset) * sys.cog_scale;
   } else {
     sx = 0.f; sy = 0.f;

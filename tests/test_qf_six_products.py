@@ -1,0 +1,93 @@
+"""The slopes-only frame kernel takes the three moments of a sub-aperture from SIX matrix products
+(csrc/aomarl_kernels.hip: spot_qf_moments): with Wr = M Er^T, Wi = M Ei^T the one accumulator
+
+    X = (Er + Ei) Wr + (Ei - Er) Wi = G1 + (G2 - G2^T),    G1 = Er Wr + Ei Wi (symmetric),  G2 = Ei Wr
+
+gives  <M, X> = <M, G1>  (the antisymmetric part drops out against the symmetric M) and  <S, X> = 2 <S, G2>  (the
+symmetric part drops out against the antisymmetric S), so G2 is never formed.  Checked here on the CPU: the identity
+for arbitrary real Er, Ei in float64, and the float32 centroids of both forms against the definition (zero-padded FFT,
+|.|^2, binning, moments: tools/qf_cog_check.py) on the geometry of both shipped sizes."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools"))
+import qf_cog_check as qf  # noqa: E402
+
+SIZES = ("production_sh_10x10_2m", "production_sh_40x40_8m_3layers")
+
+
+def _wfs(name):
+    from ao_marl_amd import params, geometry
+    return geometry.build_system(params.builtin(name)).wfss[0]
+
+
+def _moments7(M, S, Er, Ei):
+    Wr, Wi, V = M @ Er.T, M @ Ei.T, S @ Er.T
+    return (M * (Er @ Wr + Ei @ Wi)).sum(), (S * (Ei @ Wr)).sum(), (M * (Ei @ V)).sum()
+
+
+def _moments6(M, S, Er, Ei):
+    Wr, Wi, V = M @ Er.T, M @ Ei.T, S @ Er.T
+    X = (Er + Ei) @ Wr + (Ei - Er) @ Wi
+    return (M * X).sum(), 0.5 * (S * X).sum(), (M * (Ei @ V)).sum()
+
+
+def test_one_accumulator_holds_both_moments_for_any_real_field():
+    """Nothing in the identity uses |E| = 1 or the mask: arbitrary real Er, Ei, with and without masked points.
+    Bound: every moment is a sum of 16^4 products of magnitude <= |M|max |S|max |E|max^2, accumulated in float64
+    (eps 1.1e-16); the two forms differ by round-off only, a few hundred eps of the sum of magnitudes at the very
+    worst -- 1e-10 of that scale is four orders above it and ten below anything a slope could notice."""
+    M, S = qf.kernels()
+    rng = np.random.default_rng(11)
+    for trial in range(60):
+        Er, Ei = rng.normal(size=(2, 16, 16)) * rng.uniform(0.1, 30.0)
+        if trial % 3:
+            mask = rng.random((16, 16)) > 0.3
+            Er, Ei = Er * mask, Ei * mask
+        if trial % 5 == 0:
+            Ei = Ei * 0.0                                         # a purely real field: both first moments vanish
+        a, b = _moments7(M, S, Er, Ei), _moments6(M, S, Er, Ei)
+        A, Sa, E2 = np.abs(M), np.abs(S), np.abs(Er) + np.abs(Ei)
+        scale = max((A * (E2 @ A @ E2.T)).sum(), (Sa * (E2 @ A @ E2.T)).sum(), (A * (E2 @ Sa @ E2.T)).sum())
+        for x, y in zip(a, b):
+            assert abs(x - y) <= 1e-10 * scale, (trial, x, y, scale)
+
+
+@pytest.mark.parametrize("name", SIZES)
+def test_float32_centroids_of_both_forms_match_the_definition(name):
+    """Both forms with float32 operands against the float64 definition, 1e-5 pixels (the bound of
+    tests/test_qf_cog_identity.py: 2.6e-6 arcsec, far inside the 1e-4 arcsec the slopes are held to), with tilts of
+    up to +-6 revolutions across the sub-aperture per axis (4 revolutions carry the spot to the edge of the binned
+    window, beyond that it wraps around) on top of random phase and a piston of hundreds of revolutions."""
+    w = _wfs(name)
+    assert (w.Nfft, w.pdiam, w.npix, w.nrebin) == (64, 16, 16, 2)
+    M, S = qf.kernels()
+    rng = np.random.default_rng(23)
+    worst = {"seven": 0.0, "six": 0.0}
+    for trial in range(80):
+        amp = (rng.random((16, 16)) > (0.0 if trial % 2 else 0.25)).astype(float)
+        tx, ty = rng.uniform(-6.0, 6.0, size=2)                   # revolutions across the 16 pupil pixels
+        tilt = np.add.outer(np.arange(16) * ty / 16.0, np.arange(16) * tx / 16.0)
+        ph = rng.normal(size=(16, 16)) * rng.uniform(0, 0.3) + tilt + rng.integers(-400, 400)
+        a = qf.cog_definition(w, ph, amp)
+        for form, f in (("seven", qf.cog_quadratic_form), ("six", qf.cog_quadratic_form_six)):
+            b = f(M, S, ph, amp, np.float64)
+            c = f(M, S, ph, amp, np.float32)
+            assert abs(a[0] - b[0]) < 1e-6 and abs(a[1] - b[1]) < 1e-6 and abs(a[2] - b[2]) < 1e-6 * a[2], (form, trial)
+            worst[form] = max(worst[form], abs(a[0] - c[0]), abs(a[1] - c[1]))
+            assert abs(a[0] - c[0]) < 1e-5 and abs(a[1] - c[1]) < 1e-5, (form, trial, a, c)
+    print("worst float32 centroid error, pixels:", worst)
+
+
+def test_six_product_form_is_the_quadratic_form_of_the_tool():
+    """tools/qf_cog_check.py's six-product function on an arbitrary (non-unit-modulus) field equals the moments above."""
+    M, S = qf.kernels()
+    rng = np.random.default_rng(5)
+    Er, Ei = rng.normal(size=(2, 16, 16))
+    s0, ty, tx = _moments6(M, S, Er, Ei)
+    cx, cy, t0 = qf.cog_quadratic_form_six(M, S, None, None, np.float64, field=(Er, Ei))
+    assert abs(t0 - s0) <= 1e-12 * abs(s0)
+    assert abs(cx - (7.5 + 2 * tx / s0)) < 1e-12 and abs(cy - (7.5 + 2 * ty / s0)) < 1e-12
