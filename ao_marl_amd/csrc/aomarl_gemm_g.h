@@ -326,6 +326,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_g(const GemmGArgs a) {
 // gradient; the policy's first layer and the critics' hidden layer on the gathered batch) share a grid instead of
 // meeting through events on two streams (an event record or wait on the critical stream cost 6 - 7.5 us each,
 // profiles/r05a_sac_update_timeline.txt).  A workgroup belongs to one problem: the form switch is block-uniform.
+// (static: this header is included by more than one translation unit of the library.)
 #define GG_MAXP 3
 struct GemmGMulti {
   int np;
@@ -334,7 +335,7 @@ struct GemmGMulti {
   GemmGArgs p[GG_MAXP];
 };
 
-__global__ __launch_bounds__(256, 2) void k_gemm_g_multi(const GemmGMulti mp) {
+static __global__ __launch_bounds__(256, 2) void k_gemm_g_multi(const GemmGMulti mp) {
   const int w = gemm_g_tile_of_block();
   if (w >= mp.tile_end[mp.np - 1]) return;
   int i = 0;

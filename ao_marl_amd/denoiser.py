@@ -159,3 +159,330 @@ class SubapDenoiser(object):
             y = self.forward(t.transpose(1, 2).unsqueeze(1))
             t.copy_(y.squeeze(1).transpose(1, 2))
         return bincube
+
+
+# ------------------------------------------------------------------------------------------------
+# Training of the reference's module (autoencoder_models.py:130-197) on pairs recorded as
+# OfflineDatasetObtainer.record_data records them (src/autoencoder/obtain_dataset_autoencoder.py:
+# 66-109).  The reference ships no training loop: the loss (mean squared error) and the optimiser
+# (torch.optim.Adam's formula) are this project's choice.  On the GPU the whole step -- forward,
+# loss, backward, Adam -- is the library's (aomarl_denoiser_trainer_*, csrc/aomarl_denoise_train.hip);
+# the autograd statement below is its definition and the CPU path.
+# ------------------------------------------------------------------------------------------------
+WANT_SHAPES = {"encoder1": (16, 1, 3, 3), "encoder2": (32, 16, 3, 3), "encoder3": (64, 32, 3, 3),
+               "decoder1": (64, 32, 4, 4), "decoder2": (32, 16, 4, 4), "decoder3": (16, 1, 3, 3)}
+PARAM_KEYS = tuple("%s.%s" % (k, p) for k in KEYS for p in ("weight", "bias"))
+
+
+def net_forward(w, x):
+    """autoencoder_models.py:161-197 (no batch norm, sigmoid branch off) on a dict of tensors;
+    differentiable.  x: [N, 1, 16, 16] in the reference's orientation."""
+    x = F.relu(F.conv2d(x, w["encoder1.weight"], w["encoder1.bias"], padding=1))
+    x = F.max_pool2d(x, 2)
+    x = F.relu(F.conv2d(x, w["encoder2.weight"], w["encoder2.bias"], padding=1))
+    x = F.max_pool2d(x, 2)
+    x = F.relu(F.conv2d(x, w["encoder3.weight"], w["encoder3.bias"], padding=1))
+    x = F.relu(F.conv_transpose2d(x, w["decoder1.weight"], w["decoder1.bias"], stride=2, padding=1))
+    x = F.relu(F.conv_transpose2d(x, w["decoder2.weight"], w["decoder2.bias"], stride=2, padding=1))
+    return F.conv_transpose2d(x, w["decoder3.weight"], w["decoder3.bias"], stride=1, padding=1)
+
+
+def _tiles_to_net(t):
+    """[N, 256] tiles [y][x] -> [N, 1, 16, 16] as the network sees them ([x][y])."""
+    return t.reshape(-1, 16, 16).transpose(1, 2).unsqueeze(1)
+
+
+def fresh_state_dict(seed=0):
+    """The initialisation of the reference's layer constructors (autoencoder_models.py:137-144:
+    torch's defaults for Conv2d / ConvTranspose2d), from a seed of its own (the global generator is
+    left as it was)."""
+    import torch.nn as nn
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(int(seed))
+        mods = {"encoder1": nn.Conv2d(1, 16, 3, 1, 1), "encoder2": nn.Conv2d(16, 32, 3, 1, 1),
+                "encoder3": nn.Conv2d(32, 64, 3, 1, 1), "decoder1": nn.ConvTranspose2d(64, 32, 4, 2, 1),
+                "decoder2": nn.ConvTranspose2d(32, 16, 4, 2, 1), "decoder3": nn.ConvTranspose2d(16, 1, 3, 1, 1)}
+    return {"%s.%s" % (k, p): getattr(mods[k], p).detach().clone() for k in KEYS for p in ("weight", "bias")}
+
+
+def synthetic_pairs(n, seed=0, peak=60.0):
+    """Seeded synthetic training pairs (tests, tools): a Gaussian spot of random centre and peak
+    <= `peak`, noisy = Poisson(clean) + 3 N(0, 1).  Returns (noisy, clean), [n, 256] float32 tiles."""
+    g = torch.Generator().manual_seed(int(seed))
+    yy, xx = torch.meshgrid(torch.arange(16.), torch.arange(16.), indexing="ij")
+    c = 7.5 + 2 * torch.randn(n, 2, generator=g)
+    clean = peak * torch.rand(n, 1, 1, generator=g) * \
+        torch.exp(-((yy - c[:, :1, None]) ** 2 + (xx - c[:, 1:, None]) ** 2) / 4.5)
+    noisy = torch.poisson(clean, generator=g) + 3 * torch.randn(n, 16, 16, generator=g)
+    return noisy.reshape(n, 256).contiguous(), clean.reshape(n, 256).contiguous()
+
+
+class DenoiserTrainer(object):
+    """One Adam step on mean((net(noisy) - clean)^2) per call.
+
+    native=True (default on a GPU in float32): aomarl_denoiser_trainer_step, everything on the
+    device, no synchronisation.  native=False: the same step stated with torch autograd and
+    torch.optim.Adam's formula (any device and dtype) -- the definition the native path is tested
+    against, and the CPU path.  noisy / clean: [N, 256] tiles [y][x] as the bincube holds them."""
+
+    def __init__(self, state_dict=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, device="cuda:0",
+                 seed=0, native=None, dtype=torch.float32, max_batch=4096):
+        self.device, self.dtype = torch.device(device), dtype
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        if not self.eps > 0.0:
+            # a parameter whose gradient is exactly zero (the padded weight rows of the native step among them) would
+            # be updated by 0 / 0
+            raise ValueError("DenoiserTrainer: eps must be positive, got %r" % (eps,))
+        if state_dict is None:
+            state_dict = fresh_state_dict(seed)
+        state_dict = state_dict.get("state_dict", state_dict)
+        shapes = {k: tuple(state_dict[k + ".weight"].shape) for k in KEYS}
+        if shapes != WANT_SHAPES:
+            raise ValueError("unexpected autoencoder layout %r" % (shapes,))
+        if native is None:
+            native = self.device.type == "cuda" and dtype == torch.float32
+        if native and not (self.device.type == "cuda" and dtype == torch.float32):
+            raise ValueError("the native training step is float32 on a GPU (native=False for %s on %s)"
+                             % (dtype, self.device))
+        self.native, self.max_batch, self.steps = bool(native), int(max_batch), 0
+        self._handle = None
+        if self.native:
+            from . import libaomarl as la
+            host = {k: state_dict[k].detach().to("cpu", torch.float32).contiguous().numpy() for k in PARAM_KEYS}
+            fp = C.POINTER(C.c_float)
+            wt = (fp * 6)(*[host[k + ".weight"].ctypes.data_as(fp) for k in KEYS])
+            bs = (fp * 6)(*[host[k + ".bias"].ctypes.data_as(fp) for k in KEYS])
+            h = C.c_void_p()
+            with torch.cuda.device(self.device):
+                la.check(la.load().aomarl_denoiser_trainer_create(
+                        wt, bs, self.lr, self.betas[0], self.betas[1], self.eps, self.max_batch, C.byref(h)))
+            self._handle = h
+        else:
+            self.w = {k: state_dict[k].detach().to(self.device, dtype).clone().requires_grad_(True)
+                      for k in PARAM_KEYS}
+            self.m = {k: torch.zeros_like(v) for k, v in self.w.items()}
+            self.v = {k: torch.zeros_like(v) for k, v in self.w.items()}
+
+    def __del__(self):
+        try:
+            if getattr(self, "_handle", None):
+                from . import libaomarl as la
+                la.load().aomarl_denoiser_trainer_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+    # ---------------------------------------------------------------- native plumbing
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _check_pairs(self, noisy, clean):
+        for t in (noisy, clean):
+            if t.dim() != 2 or t.shape[1] != 256 or t.shape != noisy.shape or t.shape[0] < 1:
+                raise ValueError("noisy / clean: [N, 256] tiles, got %s and %s" % (tuple(noisy.shape), tuple(clean.shape)))
+        if self.native:
+            noisy = noisy.to(self.device, torch.float32).contiguous()
+            clean = clean.to(self.device, torch.float32).contiguous()
+        else:
+            noisy, clean = noisy.to(self.device, self.dtype), clean.to(self.device, self.dtype)
+        return noisy, clean
+
+    def _out_tensors(self):
+        out = {k: torch.empty(WANT_SHAPES[k.split(".")[0]] if k.endswith("weight") else
+                              (WANT_SHAPES[k.split(".")[0]][0 if k.startswith("enc") else 1],),
+                              dtype=torch.float32, device=self.device) for k in PARAM_KEYS}
+        vp = C.c_void_p
+        wt = (vp * 6)(*[out[k + ".weight"].data_ptr() for k in KEYS])
+        bs = (vp * 6)(*[out[k + ".bias"].data_ptr() for k in KEYS])
+        return out, wt, bs
+
+    # ---------------------------------------------------------------- the step
+    def _loss_autograd(self, noisy, clean):
+        return ((net_forward(self.w, _tiles_to_net(noisy)) - _tiles_to_net(clean)) ** 2).mean()
+
+    def grads(self, noisy, clean):
+        """(loss, {key: gradient}) of the batch at the current weights, without an update."""
+        noisy, clean = self._check_pairs(noisy, clean)
+        if self.native:
+            from . import libaomarl as la
+            out, wt, bs = self._out_tensors()
+            loss = torch.empty((), dtype=torch.float32, device=self.device)
+            la.check(la.load().aomarl_denoiser_trainer_grads(
+                    self._handle, noisy.data_ptr(), clean.data_ptr(), noisy.shape[0], wt, bs, loss.data_ptr(),
+                    self._stream()))
+            return loss, out
+        loss = self._loss_autograd(noisy, clean)
+        g = torch.autograd.grad(loss, [self.w[k] for k in PARAM_KEYS])
+        return loss.detach(), dict(zip(PARAM_KEYS, g))
+
+    def step(self, noisy, clean):
+        """One Adam step; returns the loss BEFORE the update (device scalar, no synchronisation)."""
+        if self.native:
+            from . import libaomarl as la
+            noisy, clean = self._check_pairs(noisy, clean)
+            loss = torch.empty((), dtype=torch.float32, device=self.device)
+            la.check(la.load().aomarl_denoiser_trainer_step(
+                    self._handle, noisy.data_ptr(), clean.data_ptr(), noisy.shape[0], loss.data_ptr(), self._stream()))
+            self.steps += 1
+            return loss
+        loss, g = self.grads(noisy, clean)
+        self.steps += 1
+        b1, b2 = self.betas
+        bc1, bc2 = 1.0 - b1 ** self.steps, 1.0 - b2 ** self.steps
+        with torch.no_grad():                  # torch.optim.Adam (no weight decay, no amsgrad)
+            for k in PARAM_KEYS:
+                self.m[k].mul_(b1).add_(g[k], alpha=1.0 - b1)
+                self.v[k].mul_(b2).addcmul_(g[k], g[k], value=1.0 - b2)
+                denom = (self.v[k].sqrt() / (bc2 ** 0.5)).add_(self.eps)
+                self.w[k].addcdiv_(self.m[k], denom, value=-self.lr / bc1)
+        return loss
+
+    @torch.no_grad()
+    def forward(self, noisy):
+        """The current network on [N, 256] tiles (tensor-library statement), tiles back."""
+        sd = self.state_dict()
+        w = {k: v.to(noisy.device, self.dtype) for k, v in sd.items()}
+        y = net_forward(w, _tiles_to_net(noisy.to(self.dtype)))
+        return y.squeeze(1).transpose(1, 2).reshape(-1, 256)
+
+    @torch.no_grad()
+    def loss(self, noisy, clean, chunk=65536):
+        """mean((net(noisy) - clean)^2) at the current weights, no gradient (held-out sets)."""
+        tot = torch.zeros((), dtype=torch.float64, device=noisy.device)
+        for i0 in range(0, noisy.shape[0], chunk):
+            d = self.forward(noisy[i0:i0 + chunk]) - clean[i0:i0 + chunk].to(self.dtype)
+            tot += (d.double() ** 2).sum()
+        return tot / (noisy.shape[0] * 256)
+
+    # ---------------------------------------------------------------- results
+    def state_dict(self):
+        """The weights in the reference checkpoint's layout (what SubapDenoiser takes)."""
+        if self.native:
+            from . import libaomarl as la
+            out, wt, bs = self._out_tensors()
+            la.check(la.load().aomarl_denoiser_trainer_get(self._handle, wt, bs, self._stream()))
+            return out
+        return {k: v.detach().clone() for k, v in self.w.items()}
+
+    def denoiser(self, **kw):
+        kw.setdefault("device", self.device)
+        return SubapDenoiser({k: v.float() for k, v in self.state_dict().items()}, **kw)
+
+    def save(self, path):
+        """In the layout SubapDenoiser.load reads (plain float32 tensors on the host)."""
+        torch.save({k: v.detach().to("cpu", torch.float32).contiguous() for k, v in self.state_dict().items()}, path)
+
+
+def _recording_supervisor(env_or_supervisor):
+    """The supervisor to record on; refuses the call orders in which the frame the loop imaged is
+    not the one its screens and mirrors stand on."""
+    sup = getattr(env_or_supervisor, "supervisor", env_or_supervisor)
+    env = env_or_supervisor if sup is not env_or_supervisor else None
+    if env is not None and getattr(env, "frame_pipeline", False) is not False:
+        raise RuntimeError("record_pairs: the pipelined call order (frame_pipeline=%r) images frames one step ahead "
+                           "of the chains; build the environment with frame_pipeline=False" % (env.frame_pipeline,))
+    sim = sup.sim
+    if getattr(sim, "_twin", None) is not None:
+        raise RuntimeError("record_pairs: the frame pipeline is enabled on this simulator (frame in flight: %s); "
+                           "switch it off behind a reset (enable_frame_pipeline(False))" % (sim.frame_pipeline_state()[0],))
+    if sup.prefetch_atmos or getattr(sim, "prefetch", False) or getattr(sim, "pending_atmos", False):
+        raise RuntimeError("record_pairs: the screens run one frame ahead (prefetch_atmos): the noise-free twin would "
+                           "image the NEXT frame's atmosphere; build the supervisor with prefetch_atmos=False")
+    if getattr(sup, "reset_prefetch", None) is not None:
+        raise RuntimeError("record_pairs: a prefetched reset (reset_prefetch=%r) is not supported while recording"
+                           % (sup.reset_prefetch,))
+    if sup.autoencoder is not None:
+        raise RuntimeError("record_pairs: the loop is recorded on the NOISY sensor (obtain_dataset_autoencoder.py:"
+                           "66-109); build the supervisor without an autoencoder")
+    if sup.geo is not None:
+        raise NotImplementedError("record_pairs: the plain integrator loop only (no geometric twin)")
+    if not float(sup.s.noise) >= 0.0:
+        raise ValueError("record_pairs: the sensor is noise-free (noise = %g): noisy and clean would be the same image"
+                         % float(sup.s.noise))
+    return sup
+
+
+@torch.no_grad()
+def record_pairs(env_or_supervisor, n_frames, *, reset=True, stride=1, max_pairs=None, return_counts=False):
+    """OfflineDatasetObtainer.record_data (obtain_dataset_autoencoder.py:66-109) on the device: the
+    loop runs closed on the noisy sensor with the integrator alone; every frame gives the sensor's
+    image and the image a noise-free twin sensor forms of the SAME phase (same screens, same mirror
+    shape: the second formation runs right behind the loop's own, without noise, and the frame
+    counter the noise generator is keyed by is put back, so the loop is not perturbed).
+
+    Both call orders of the supervisor are recorded as the supervisor itself runs them: the plain one
+    (the target traced in next_part_one) and modification_online, the reference's pure_delay_0, which
+    is how the reference's recorder runs (the target traced behind apply_control; the sensor's path is
+    the same in both).  The frame is always formed by the order's own library calls: the
+    supervisor's next_part_one_split, a timing switch that forms the same frame stage by stage, is not
+    consulted.  keep_wfs_phase is honoured (the frame's sensor phase is kept as next_part_one keeps it).
+
+    Returns (noisy, clean), device tensors [pairs, 256] of [y][x] tiles in (frame, env, subap)
+    order.  stride: keep every stride-th sub-aperture image (the offset rotates with the frame, so
+    the number kept can differ by one between frames); max_pairs: raise the stride so that at most
+    that many pairs are kept (one frame of 256 environments of the 40x40 sensor is 307 200 pairs,
+    630 MB).  return_counts: also return the list of pairs kept per frame, (noisy, clean, counts)."""
+    sup = _recording_supervisor(env_or_supervisor)
+    sim = sup.sim
+    if sim.s.npix * sim.s.npix != 256:
+        raise ValueError("record_pairs: the denoiser takes 16 x 16 spot images, this sensor has %d x %d" % (sim.s.npix, sim.s.npix))
+    per_frame = sim.nenv * sim.s.nvalid
+    stride = max(1, int(stride))
+    if max_pairs is not None:
+        while n_frames * ((per_frame + stride - 1) // stride) > int(max_pairs):
+            stride += 1
+    if reset:
+        sup.reset()
+    kept = [len(range((f % stride), per_frame, stride)) for f in range(n_frames)]
+    noisy = torch.empty(sum(kept), 256, dtype=torch.float32, device=sim.device)
+    clean = torch.empty_like(noisy)
+    at = 0
+    for f in range(n_frames):
+        # the loop's own frame, exactly the plain call order's (VecRlSupervisor.next_part_one), with the cube kept
+        sup._check_atmos_change()
+        sup.materialize_control()
+        sup._err_stale = False
+        if sup.pure_delay_0:                    # no target trace here (rlSupervisor.py:964-965): the sensor's path alone
+            sup._move_or_keep(True)
+            sim.comp_image(noise=True, write_bincube=True, cog=True)
+            sim.do_control()
+        else:
+            sim.next_part_one(write_bincube=True)
+        cube = sim.t["bincube"].view(per_frame, 256)
+        noisy[at:at + kept[f]].copy_(cube[f % stride::stride])
+        # the noise-free twin: the same phase imaged once more (params.py: the twin WFS is not simulated)
+        frame = sim.t["frame"].clone()
+        sim.comp_image(noise=False, write_bincube=True, cog=False)
+        clean[at:at + kept[f]].copy_(cube[f % stride::stride])
+        sim.t["frame"].copy_(frame)
+        at += kept[f]
+        if sup.keep_wfs_phase:
+            sup._snap_wfs_phase()
+        sup.iter += 1
+        sup.next_part_two(None, linear_control=True)
+    return (noisy, clean, kept) if return_counts else (noisy, clean)
+
+
+def train_denoiser(env_or_supervisor, n_frames, n_steps, batch=256, *, held_out_frames=1, seed=0,
+                   state_dict=None, lr=1e-3, stride=1, max_pairs=None, native=None):
+    """Record n_frames + held_out_frames frames, train on a device-side shuffle of the first
+    n_frames, and report on the rest.  Returns (trainer, {"held_out": loss on the held-out frames,
+    "identity": mean((noisy - clean)^2) on them, "train": [n_steps] losses (device), "pairs_per_frame": what
+    record_pairs kept of every frame, "n_train": the pairs of the first n_frames of them})."""
+    sup = _recording_supervisor(env_or_supervisor)
+    noisy, clean, kept = record_pairs(sup, n_frames + held_out_frames, stride=stride, max_pairs=max_pairs,
+                                      return_counts=True)
+    ntrain = sum(kept[:n_frames])               # whole frames: no held-out frame is trained on
+    tr = DenoiserTrainer(state_dict, lr=lr, device=noisy.device, seed=seed, native=native, max_batch=batch)
+    g = torch.Generator(device=noisy.device).manual_seed(int(seed))
+    losses = torch.empty(n_steps, dtype=torch.float32, device=noisy.device)
+    perm, at = torch.randperm(ntrain, generator=g, device=noisy.device), 0
+    for k in range(n_steps):
+        if at + batch > ntrain:
+            perm, at = torch.randperm(ntrain, generator=g, device=noisy.device), 0
+        idx = perm[at:at + batch]
+        at += batch
+        losses[k] = tr.step(noisy[idx], clean[idx])
+    hn, hc = noisy[ntrain:], clean[ntrain:]
+    return tr, {"held_out": tr.loss(hn, hc), "identity": ((hn - hc).double() ** 2).mean(), "train": losses,
+                "pairs_per_frame": kept, "n_train": ntrain}

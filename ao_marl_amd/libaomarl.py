@@ -156,6 +156,13 @@ SYMBOLS = [
     ("aomarl_denoiser_apply_split_f16", _i, [_vp, _vp, C.c_longlong, _vp]),
     ("aomarl_denoiser_overflow", _i, [_vp, C.POINTER(C.c_uint), _vp]),
     ("aomarl_denoiser_destroy", _i, [_vp]),
+    ("aomarl_denoiser_trainer_create", _i, [C.POINTER(_fp), C.POINTER(_fp), C.c_double, C.c_double, C.c_double,
+                                            C.c_double, _i, C.POINTER(C.c_void_p)]),
+    ("aomarl_denoiser_trainer_destroy", _i, [_vp]),
+    ("aomarl_denoiser_trainer_step", _i, [_vp, _vp, _vp, C.c_longlong, _vp, _vp]),
+    ("aomarl_denoiser_trainer_grads", _i, [_vp, _vp, _vp, C.c_longlong, C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_void_p), _vp, _vp]),
+    ("aomarl_denoiser_trainer_get", _i, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _vp]),
     ("aomarl_target_psf_buffer", _i, _range + [_vp]),
     ("aomarl_set_geo", _i, [_vp, _fp]),
     ("aomarl_geo_workspace_floats", C.c_size_t, [_vp, _i]),

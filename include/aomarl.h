@@ -608,6 +608,34 @@ int aomarl_denoiser_apply_split_f16(aomarl_denoiser *dn, float *cube, long long 
  * aomarl_denoiser_apply_f32.  ao_marl_amd.denoiser checks it at every episode boundary. */
 int aomarl_denoiser_overflow(aomarl_denoiser *dn, unsigned *count, void *stream);
 int aomarl_denoiser_destroy(aomarl_denoiser *dn);
+/* Training of the WFS-image denoiser (the module: src/autoencoder/autoencoder_models.py:130-197; the pairs it is
+ * trained on: src/autoencoder/obtain_dataset_autoencoder.py:66-109.  The reference ships no training loop: the
+ * loss, the mean squared error, and the optimiser, torch.optim.Adam's formula, are this library's choice).
+ * weights / biases: 6 HOST arrays each in the checkpoint's layouts, as aomarl_denoiser_create takes them; any other
+ * layer shape cannot be expressed.  lr, beta1, beta2, eps: torch.optim.Adam's (no weight decay; doubles, as torch
+ * holds them; eps > 0).  max_batch sizes the workspace (about 300 KB per image, capped at 2048 images); larger batches are processed in passes of that size, their gradients added in a fixed order.
+ * All products on fp32 matrix instructions; every sum over images and positions in a fixed order (no
+ * floating-point atomics): the same inputs give the same bits. */
+typedef struct aomarl_denoiser_trainer aomarl_denoiser_trainer;
+int aomarl_denoiser_trainer_create(const float *const *weights, const float *const *biases, double lr,
+                                   double beta1, double beta2, double eps, int max_batch,
+                                   aomarl_denoiser_trainer **out);
+int aomarl_denoiser_trainer_destroy(aomarl_denoiser_trainer *tr);
+/* One optimisation step on `nimg` pairs: forward (autoencoder_models.py:176-197, sigmoid branch off), loss =
+ * mean((net(noisy) - clean)^2) over nimg * 256 pixels, backward, Adam with bias correction.  noisy, clean:
+ * device [nimg][256], tiles [y][x] (the network sees them transposed, as in aomarl_denoiser_apply).
+ * loss_out: device float (the loss BEFORE the update) or NULL.  Asynchronous on `stream`. */
+int aomarl_denoiser_trainer_step(aomarl_denoiser_trainer *tr, const float *noisy, const float *clean,
+                                 long long nimg, float *loss_out, void *stream);
+/* The same gradients without the update.  grads_w / grads_b: 6 DEVICE arrays each in the checkpoint's layouts
+ * (an entry may be NULL). */
+int aomarl_denoiser_trainer_grads(aomarl_denoiser_trainer *tr, const float *noisy, const float *clean,
+                                  long long nimg, float *const *grads_w, float *const *grads_b,
+                                  float *loss_out, void *stream);
+/* The current weights into 6 + 6 DEVICE arrays in the checkpoint's layouts (what aomarl_denoiser_create and
+ * SubapDenoiser take, once on the host). */
+int aomarl_denoiser_trainer_get(aomarl_denoiser_trainer *tr, float *const *weights, float *const *biases,
+                                void *stream);
 /* PSF window + phase variance of st->tar_phase as it stands (pending, like aomarl_target_psf) */
 int aomarl_target_psf_buffer(aomarl_ctx *ctx, aomarl_state *st, int env_begin, int env_count,
                              void *stream);
