@@ -163,6 +163,12 @@ SYMBOLS = [
     ("aomarl_denoiser_trainer_grads", _i, [_vp, _vp, _vp, C.c_longlong, C.POINTER(C.c_void_p),
                                            C.POINTER(C.c_void_p), _vp, _vp]),
     ("aomarl_denoiser_trainer_get", _i, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _vp]),
+    ("aomarl_roket_create", _i, [_vp, C.POINTER(C.c_void_p)]),
+    ("aomarl_roket_destroy", _i, [_vp]),
+    ("aomarl_roket_step", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    ("aomarl_roket_moments", _i, [_vp, _vp, _vp, C.POINTER(C.c_longlong), _vp]),
+    ("aomarl_roket_reset", _i, [_vp]),
+    ("aomarl_roket_history", _i, [_vp, _vp, _vp, _vp]),
     ("aomarl_target_psf_buffer", _i, _range + [_vp]),
     ("aomarl_set_geo", _i, [_vp, _fp]),
     ("aomarl_geo_workspace_floats", C.c_size_t, [_vp, _i]),
@@ -227,6 +233,12 @@ class EnvGlue(C.Structure):
 
 
 ENV_STEP_UNFUSED = 1
+
+
+class RoketDesc(C.Structure):
+    """aomarl_roket_desc (include/aomarl.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("nenv", "nactu", "ld_actu", "nmodes", "nfiltered", "delay")] + \
+               [("g", C.c_float), ("gamma", C.c_float), ("RD", _fp), ("P", _fp), ("Btt", _fp)]
 
 
 class AomarlError(RuntimeError):

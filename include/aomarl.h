@@ -636,6 +636,42 @@ int aomarl_denoiser_trainer_grads(aomarl_denoiser_trainer *tr, const float *nois
  * SubapDenoiser take, once on the host). */
 int aomarl_denoiser_trainer_get(aomarl_denoiser_trainer *tr, float *const *weights, float *const *biases,
                                 void *stream);
+/* ROKET error breakdown (guardians/roket_generalized_rl.py:189-284, 441-480): the loop filters of the seven
+ * contributors {noise, trunc (non linearity), alias, H_com (filtered modes), bp (bandwidth), tomo, zeta} and the modal
+ * moments of their covariance table, for nenv environments at once.  The reference keeps [n_iter][nactu] histories on
+ * the host; this object keeps the last `delay` frames on the device and sums the moments as it goes.
+ * RD = cmat . imat [nactu][nactu], P [nmodes][nactu], Btt [nactu][nmodes]: HOST arrays, row-major, copied.
+ * gRD = g * gamma * RD is formed inside (:161).  delay = int(p_controllers[0].delay) + 1 (:163), 1..64.
+ * nfiltered: the modes [-nfiltered-2 : -2] are the filtered ones (:258-264). */
+typedef struct {
+  int32_t nenv, nactu, ld_actu, nmodes, nfiltered, delay;
+  float g, gamma;
+  const float *RD, *P, *Btt;
+} aomarl_roket_desc;
+typedef struct aomarl_roket aomarl_roket;
+int aomarl_roket_create(const aomarl_roket_desc *desc, aomarl_roket **out);
+int aomarl_roket_destroy(aomarl_roket *r);
+/* Frame t of the breakdown.  derr, E, F, ageom, B, G, rl_com: device [nenv][ld_actu], this frame's
+ * -cmat.slopes of the loop (derr), of the noise-free image (E), of the geometric slopes (F), of the geometric slopes
+ * of the DM-orthogonal phase (ageom), the geometric controller's commands in the target direction (B) and in the WFS
+ * direction (G), and Btt . (the policy's modes) (rl_com).  G == NULL means G = B: tomography is identically zero and
+ * its products are skipped.  rl_com == NULL: zeta stays zero.  Then
+ *   noise_buf = derr - E, trunc_buf = E - gamma F, H_com / mod_com / wf_com from P, Btt and the filtered range,
+ *   tomo_buf = mod_com - wf_com, and  x[t] = x[t-1] - gRD x[t-delay] + u[t-delay]  with u = g noise_buf,
+ *   g trunc_buf, gamma g ageom, rl_com; bandwidth takes -(mod_com[t] - mod_com[t-1]) undelayed, tomography
+ *   -g gamma RD tomo_buf[t-delay], as the reference does.  History before frame 0 is zero.
+ * accumulate != 0: y_k = P x_k and, per environment and mode, S1[k] += y_k, S2[k <= l] += y_k y_l in double.
+ * Every sum in a fixed order, no atomics: the same inputs give the same bits.  Asynchronous on `stream`. */
+int aomarl_roket_step(aomarl_roket *r, const float *derr, const float *E, const float *F, const float *ageom,
+                      const float *B, const float *G, const float *rl_com, int accumulate, void *stream);
+/* S1_out: DEVICE double [nenv][7][nmodes]; S2_out: DEVICE double [nenv][28][nmodes], pairs (k, l), k <= l, k major;
+ * frames_out: HOST, the number of accumulated frames.  Any may be NULL. */
+int aomarl_roket_moments(aomarl_roket *r, double *S1_out, double *S2_out, long long *frames_out, void *stream);
+/* zero histories, moments and the frame counter (synchronises the device) */
+int aomarl_roket_reset(aomarl_roket *r);
+/* x_out: DEVICE [7][nenv][nactu], the contributors of the last frame; bufs_out: DEVICE [4][nenv][nactu], its
+ * noise_buf, trunc_buf, tomo_buf, mod_com.  Either may be NULL. */
+int aomarl_roket_history(aomarl_roket *r, float *x_out, float *bufs_out, void *stream);
 /* PSF window + phase variance of st->tar_phase as it stands (pending, like aomarl_target_psf) */
 int aomarl_target_psf_buffer(aomarl_ctx *ctx, aomarl_state *st, int env_begin, int env_count,
                              void *stream);

@@ -1,0 +1,86 @@
+"""ROKET error breakdown of a closed loop (ao_marl_amd.roket.VecRoket) from the command line.
+
+    python tools/error_budget.py --params production_sh_10x10_2m --nenv 4 --frames 300 --preloop 50
+    python tools/error_budget.py --params ... --agents 2 --checkpoints DIR     # DIR: one actor file per agent
+
+Without --checkpoints the integrator alone is analysed (6 x 6 tables); with it the agents of the directory (files in
+sorted order = agent order, any of the three actor layouts BatchedSAC.load_model accepts) and zeta joins the table.
+Prints the reference's progress line every 100 frames and, at the end, the mean over environments of the per-
+contributor variance (the diagonal of cov, microns^2), the correlation table, the fitting term, the long-exposure
+Strehl and how far exp(-(variance of the sum + fitting)) closes on it."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--params", default="production_sh_10x10_2m")
+    ap.add_argument("--nenv", type=int, default=4)
+    ap.add_argument("--frames", type=int, default=300)
+    ap.add_argument("--preloop", type=int, default=50)
+    ap.add_argument("--agents", type=int, default=1, help="n_agents_modal of the layout")
+    ap.add_argument("--checkpoints", default=None, help="directory of actor checkpoints, one per agent")
+    ap.add_argument("--nfiltered", type=int, default=5)
+    ap.add_argument("--modes", type=int, nargs=2, default=None, help="n_zernike_start_end")
+    ap.add_argument("--gamma", type=float, default=1.0, help="centroid gain")
+    ap.add_argument("--accumulate-from", type=int, default=0,
+                    help="first frame of the moments (0: the reference's cov_cor, preloop included)")
+    ap.add_argument("--seed", type=int, default=200)
+    ap.add_argument("--save", default=None, help=".npz of the histories of environment 0")
+    a = ap.parse_args(argv)
+    from ao_marl_amd import roket
+    from ao_marl_amd.env import VecAoEnv
+    rl = dict(n_reverse_filtered_from_cmat=a.nfiltered)
+    if a.modes is not None:
+        rl["n_zernike_start_end"] = list(a.modes)
+    env = VecAoEnv(a.params, a.nenv, rl, n_agents_modal=a.agents, geo=True, frame_pipeline=False)
+    env.set_sim_seed(a.seed)                         # error_budget_multiple_agents.py:291-292
+    policy = None
+    if a.checkpoints:
+        from ao_marl_amd.sac import BatchedSAC
+        sac = BatchedSAC(env.layout, dict(memory_size=16))
+        files = sorted(f for f in os.listdir(a.checkpoints) if not f.startswith("."))
+        if len(files) != env.layout.n_agents:
+            raise SystemExit("--checkpoints: %d files for %d agents" % (len(files), env.layout.n_agents))
+        for i, f in enumerate(files):
+            sac.load_model(i, os.path.join(a.checkpoints, f))
+        policy = sac.policy
+    rk = roket.VecRoket(env, a.frames, a.preloop, policy=policy, gamma=a.gamma, accumulate_from=a.accumulate_from,
+                        keep_envs=(0,) if a.save else ())
+    res = rk.run()
+    names = res["contributors"]
+    cov, cor = res["cov"].mean(axis=0), res["cor"].mean(axis=0)
+    print("\n%s, %d environments, %d frames (%d preloop), moments over %d frames" %
+          (a.params, a.nenv, a.frames, a.preloop, res["frames"]))
+    print("%-16s %14s %10s" % ("contributor", "variance", "share"))
+    tot = float(np.trace(cov))
+    for k, n in enumerate(names):
+        print("%-16s %14.6e %9.1f%%" % (n, cov[k, k], 100.0 * cov[k, k] / tot if tot > 0 else 0.0))
+    print("%-16s %14.6e   (sum of the diagonal)" % ("total", tot))
+    print("%-16s %14.6e   (all pairs: variance of the sum)" % ("sum", float(cov.sum())))
+    print("\ncorrelation (mean over environments)")
+    print(" " * 16 + " ".join("%8s" % n[:8] for n in names))
+    for k, n in enumerate(names):
+        print("%-16s" % n + " ".join("%8.3f" % cor[k, l] for l in range(len(names))))
+    k = res["rad2_per_um2"]
+    fit = float(res["fitting"].mean())
+    print("\nfitting (mean phase variance behind the geometric controller) %.6e um^2 = %.5f rad^2" % (fit, fit * k))
+    budget = float(cov.sum()) * k + fit * k
+    print("budget: variance of the sum %.5f rad^2 + fitting %.5f rad^2 = %.5f rad^2 -> exp(-.) = %.4f" %
+          (float(cov.sum()) * k, fit * k, budget, float(np.exp(-budget))))
+    print("closure: exp(-budget) - SR long exposure = %+.4f" % (float(np.exp(-budget)) - float(res["SR"].mean())))
+    print("SR long exposure %.4f   SR2 = exp(-mean phase variance) %.4f" % (float(res["SR"].mean()), float(res["SR2"].mean())))
+    print("centroid gain %.4f   centroid gain 2 %.4f" % (float(res["centroid_gain"].mean()), float(res["centroid_gain2"].mean())))
+    if a.save:
+        rk.save(a.save)
+        print("histories of environment 0 -> %s" % a.save)
+    return res
+
+
+if __name__ == "__main__":
+    main()
