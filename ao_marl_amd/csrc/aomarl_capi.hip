@@ -3,6 +3,7 @@
 // Host side only sequences kernel launches on the caller's stream; no device<->host copies after
 // aomarl_create / aomarl_set_* (aomarl_reset uploads env_count seeds, 4 bytes each).
 #include "aomarl_kernels.hip"
+#include "aomarl_qf4_host.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -623,11 +624,11 @@ int aomarl_create(const aomarl_desc *d, aomarl_ctx **out) {
         s.psf_tw_f = devf;
       }
       {
-        std::vector<float> z(64 * 8, 0.f);
-        float *qt;
-        UP(float, z.data(), z.size(), qt);
-        hipLaunchKernelGGL(k_fill_qf_tab, dim3(1), dim3(128), 0, 0, qt);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { aomarl_destroy(c); return fail("create: quadratic-form constants"); }
+        // the four-product moment constants of every lane (aomarl_qf4_host.h), checked against M and S in double
+        float qtab[64 * 8];
+        if (!aomarl_qf4::build_table(qtab)) { aomarl_destroy(c); return fail("create: quadratic-form constants"); }
+        const float *qt = nullptr;
+        UP(float, qtab, 64 * 8, qt);
         s.qf_tab = qt;
       }
       UP(uint16_t, tmask.data(), tmask.size(), s.tile_mask);

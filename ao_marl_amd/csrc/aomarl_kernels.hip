@@ -1766,7 +1766,7 @@ __device__ __forceinline__ void spot_cog_f32_pk(const DevSys &sys, const DevStat
 
 // ---------------------------------------------------------------------------------------------
 // Slopes only, fp32, WITHOUT the spot: the three moments of the binned image as quadratic forms of the
-// pupil field (24 matrix instructions per sub-aperture -- six 16 x 16 x 16 products -- instead of the transform's 48).
+// pupil field (16 matrix instructions per sub-aperture -- four 16 x 16 x 16 products -- instead of the transform's 48).
 //
 // The binned image covers the central 32 x 32 frequencies f = +-(j + 1/2), j = 0 .. 15 of the half-pixel-shifted
 // 64-point transform, every one of them exactly once (npix * nrebin = 32), and the pixel coordinate of a frequency
@@ -1779,80 +1779,32 @@ __device__ __forceinline__ void spot_cog_f32_pk(const DevSys &sys, const DevStat
 //     sum I           = < M, Er M Er^T + Ei M Ei^T >
 //     sum (X - 7.5) I =  2 < M, Ei S Er^T >
 //     sum (Y - 7.5) I =  2 < S, Ei M Er^T >            (< A, B > = sum_{y', y} A[y'][y] B[y'][y])
-// The first and the third share ONE accumulator.  G1 = Er M Er^T + Ei M Ei^T is symmetric, and with G2 = Ei M Er^T
-//     X = (Er + Ei) M Er^T + (Ei - Er) M Ei^T = G1 + (G2 - G2^T):
-// the antisymmetric part drops out against the symmetric M, the symmetric part against the antisymmetric S, and
-// < S, G2 - G2^T > = 2 < S, G2 >, so that
-//     sum I = < M, X >,      sum (Y - 7.5) I = < S, X >
-// and G2 is never formed (tests/test_qf_six_products.py; same float32 error as the seven-product form).
-// -- the same numbers as transform, |.|^2, 2 x 2 binning and centre of gravity, to fp32 round-off (2e-7 pixels
-// against the 64 x 64 FFT in float64, tools/qf_cog_check.py).  Not usable with noise or when the image is wanted.
+// Both kernels factor through ONE real 16-column basis (aomarl_qf4_host.h builds it on the host, in double):
+//     M = H' H'^T,      S = H' L H'^T,      L = 2 x 2 blocks [[0, t_k], [-t_k, 0]] on eight pairs of columns,
+// so that with  P = H'^T E H' = Pr + i Pi  (complex 16 x 16: rows b belong to y, columns a to x)
+//     sum I           = |Pr|^2 + |Pi|^2
+//     sum (X - 7.5) I = 2 sum_b sum_k t_k (Pi[b][k] Pr[b][k'] - Pi[b][k'] Pr[b][k])      (k, k': the columns of pair k)
+//     sum (Y - 7.5) I = 2 sum_a sum_k t_k (Pi[k][a] Pr[k'][a] - Pi[k'][a] Pr[k][a])      (k, k': the rows of pair k)
+// (tests/test_qf_four_products.py; float32 error not above the six-product form's, tools/qf_cog_check.py)
+// -- the same numbers as transform, |.|^2, 2 x 2 binning and centre of gravity, to fp32 round-off.  Not usable with
+// noise or when the image is wanted.
 //
-// On the matrix cores: lane (q, c) holds E[y = c][x = 4q + s], which is the A operand of a product E . (..) AND
-// the B operand of a product (..) . E^T:  W = M Er^T, M Ei^T, S Er^T  (A = the constant [x' = c][x = 4q + s], 12
-// instructions) come out as [x' = 4q + r][y = c], the B operand of  (Er + Ei) W, (Ei - Er) W, Ei W  (12 instructions),
-// whose results [y' = 4q + r][y = c] meet the same constants again (M symmetric, S antisymmetric) in 6 packed
-// multiply-adds.
-struct SpotQf { f32x2 Ml, Mh, Sl, Sh; };          // M[c][4q + s], S[c - (4q + s)], s = 0 .. 3
+// On the matrix cores: lane (q, c) holds E[y = c][x = 4q + s], the A operand of E H' with the lane's constants
+// h[s] = H'[4q + s][col(c)] as the B operand (8 instructions, Er and Ei); the results [y = 4q + r][col(c)] are the B
+// operand of H'^T (E H') with the SAME four constants as the A operand (8 instructions), and P comes out as
+// [row(4q + r)][col(c)].  The table orders the basis so that the two columns of a pair sit in lanes c and c ^ 2 and
+// the two rows of a pair in registers r and r + 2 (aomarl_qf4_host.h: lane_column): the y moment is two packed
+// products of the halves of the lane's own accumulators, the x moment one quad_perm read per register.
+struct SpotQf { f32x4 h; f32x2 ky; float kx; };   // sys.qf_tab: h[s], (-2 t_{2q}, -2 t_{2q+1}), +-t of the lane's column
 
-__device__ __forceinline__ SpotQf spot_qf_consts(int lane, const float2 *sTw /* [128]: cos, sin(2 pi k / 128) */) {
-  const int q = lane >> 4, c = lane & 15;
-  float m[4], sv[4];
-#pragma unroll
-  for (int s = 0; s < 4; s++) {
-    const int d = c - (4 * q + s);
-    float a = 0.f, b = 0.f;
-    for (int j = 0; j < 16; j++) {
-      const float2 w = sTw[((2 * j + 1) * d) & 127];
-      a += w.x;
-      b = fmaf(0.5f + (float)(j >> 1), w.y, b);
-    }
-    // exact zeros of the Dirichlet kernel (even d != 0) come out as round-off: clear them
-    m[s] = (d != 0 && (d & 1) == 0) ? 0.f : 2.f * a;
-    sv[s] = 2.f * b;
-  }
-  SpotQf k;
-  k.Ml = f32x2{m[0], m[1]}; k.Mh = f32x2{m[2], m[3]};
-  k.Sl = f32x2{sv[0], sv[1]}; k.Sh = f32x2{sv[2], sv[3]};
-  return k;
-}
-
-// sys.qf_tab: the constants of every lane, once per context (the frame kernel computed them at the head of every
-// workgroup: a 128-entry twiddle table by two of its waves, a barrier, 64 LDS reads and ~250 vector instructions per
-// wave).  Same table expression, same function: the same bits.
-__global__ __launch_bounds__(128) void k_fill_qf_tab(float *__restrict__ tab) {
-  __shared__ float2 sTw[128];
-  const int tid = threadIdx.x;
-  float sn, cs;
-  sincospif((float)tid * (1.0f / 64.0f), &sn, &cs);
-  sTw[tid] = make_float2(cs, sn);
-  __syncthreads();
-  if (tid < 64) {
-    const SpotQf k = spot_qf_consts(tid, sTw);
-    float *o = tab + 8 * tid;
-    o[0] = k.Ml.x; o[1] = k.Ml.y; o[2] = k.Mh.x; o[3] = k.Mh.y;
-    o[4] = k.Sl.x; o[5] = k.Sl.y; o[6] = k.Sh.x; o[7] = k.Sh.y;
-  }
-}
-
-// The three moments of one sub-aperture, summed over the wave: returns z with  row 0 (lanes 0 .. 15): sum I = < M, X >,
-// row 1: -sum (Y - 7.5) I = < S, X > in the result layout (sign and the factors: see qf_slopes),  row 2: sum (X - 7.5) I / 2
-// = < M, G3 >  -- every lane of a row holds the total.
+// The three moments of one sub-aperture, summed over the wave: returns z with  row 0 (lanes 0 .. 15): sum I,
+// row 1: -sum (Y - 7.5) I, whole,  row 2: sum (X - 7.5) I / 2  (sign and the factors are folded into the table: see
+// qf_slopes) -- every lane of a row holds the total.
 // Round 6: 10 cross-lane instructions instead of 3 x 7 (tools/permlanebench.hip): gfx950's row swaps fold the four
 // 16-lane rows of TWO registers into one (v_permlane32_swap: the upper half of the first operand against the lower
 // half of the second -- [a_lo | b_lo] + [a_hi | b_hi]; v_permlane16_swap: the odd rows of the first against the even
-// rows of the second), so that one register carries all three sums through the four in-row DPP steps; and the two
-// products that make X share an accumulator (two packed instructions less).
+// rows of the second), so that one register carries all three sums through the four in-row DPP steps.
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-// A/B switches (make variant): A = Er + Ei, B = Ei - Er as four packed additions behind stage 1 (1) or as eight plain
-// ones the compiler spreads over stage 2 (0); X on one accumulator (0) or on two summed by two packed additions (1:
-// with packed A, B that is 114 registers, past the 112 three waves per SIMD beside a product's workgroup leave)
-#ifndef FW_QF6_PK
-#define FW_QF6_PK 1
-#endif
-#ifndef FW_QF6_ACC2
-#define FW_QF6_ACC2 0
-#endif
 __device__ __forceinline__ float swap32_add(float a, float b) {
   const u32x2 t = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
   return __uint_as_float(t[0]) + __uint_as_float(t[1]);      // rows 0, 1: a (rows 0 + 2, 1 + 3); rows 2, 3: b
@@ -1861,57 +1813,48 @@ __device__ __forceinline__ float swap16_add(float a, float b) {
   const u32x2 t = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
   return __uint_as_float(t[0]) + __uint_as_float(t[1]);      // rows: a.0 + a.1, b.0 + b.1, a.2 + a.3, b.2 + b.3
 }
+// a[lane ^ 2] * b  and  acc += a[lane ^ 2] * b  (quad_perm [2,3,0,1]; every lane is active and has its partner)
+__device__ __forceinline__ float dpp4e_mul(float a, float b) {
+  float d;
+  asm volatile("v_mul_f32_dpp %0, %1, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(d) : "v"(a), "v"(b));
+  return d;
+}
+__device__ __forceinline__ void dpp4e_fmac(float &acc, float a, float b) {
+  asm volatile("v_fmac_f32_dpp %0, %1, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(acc) : "v"(a), "v"(b));
+}
 __device__ __forceinline__ float spot_qf_moments(const SpotQf &K, const float (&er)[4], const float (&ei)[4], const f32x4 z4) {
-  const float Mc[4] = {K.Ml.x, K.Ml.y, K.Mh.x, K.Mh.y}, Sc[4] = {K.Sl.x, K.Sl.y, K.Sh.x, K.Sh.y};
-  f32x4 Wr = z4, Wi = z4, V = z4;
+  f32x4 Dr = z4, Di = z4;
 #pragma unroll
   for (int s = 0; s < 4; s++) {
-    Wr = mfma16(Mc[s], er[s], Wr);               // (M Er^T)[x'][y]
-    Wi = mfma16(Mc[s], ei[s], Wi);               // (M Ei^T)[x'][y]
-    V = mfma16(Sc[s], er[s], V);                 // (S Er^T)[x'][y]
+    Dr = mfma16(er[s], K.h[s], Dr);              // (Er H')[y][a]
+    Di = mfma16(ei[s], K.h[s], Di);              // (Ei H')[y][a]
   }
-  // A = Er + Ei, B = Ei - Er (er is dead from here)
-#if FW_QF6_PK
-  const f32x2 er01 = {er[0], er[1]}, er23 = {er[2], er[3]}, ei01 = {ei[0], ei[1]}, ei23 = {ei[2], ei[3]};
-  __builtin_amdgcn_sched_barrier(0);             // (behind stage 1: the cos / sin that made er, ei are long done)
-  const f32x2 a01 = pk_add(er01, ei01), a23 = pk_add(er23, ei23);
-  const f32x2 b01 = pk_sub(ei01, er01), b23 = pk_sub(ei23, er23);
-  PK_END_TO_MFMA();
-  const float A[4] = {a01.x, a01.y, a23.x, a23.y}, B[4] = {b01.x, b01.y, b23.x, b23.y};
-#else
-  float A[4], B[4];
+  f32x4 Pr = z4, Pi = z4;
 #pragma unroll
-  for (int s = 0; s < 4; s++) { A[s] = er[s] + ei[s]; B[s] = ei[s] - er[s]; }
-#endif
-#if FW_QF6_ACC2
-  f32x4 Xa = z4, Xb = z4, G3 = z4;
-#pragma unroll
-  for (int s = 0; s < 4; s++) {
-    Xa = mfma16(A[s], Wr[s], Xa);                // ((Er + Ei) M Er^T)[y'][y]
-    Xb = mfma16(B[s], Wi[s], Xb);                // ((Ei - Er) M Ei^T)[y'][y]
-    G3 = mfma16(ei[s], V[s], G3);                // (Ei S Er^T)[y'][y]
+  for (int r = 0; r < 4; r++) {
+    Pr = mfma16(K.h[r], Dr[r], Pr);              // (H'^T Er H')[b][a]
+    Pi = mfma16(K.h[r], Di[r], Pi);              // (H'^T Ei H')[b][a]
   }
   PK_GUARD_MFMA();
-  const f32x2 Xl = pk_add(pk_lo(Xa), pk_lo(Xb)), Xh = pk_add(pk_hi(Xa), pk_hi(Xb));
-#else
-  f32x4 X = z4, G3 = z4;
-#pragma unroll
-  for (int s = 0; s < 4; s++) {
-    X = mfma16(A[s], Wr[s], X);                  // ((Er + Ei) M Er^T + (Ei - Er) M Ei^T)[y'][y]: one accumulator
-    G3 = mfma16(ei[s], V[s], G3);                // (Ei S Er^T)[y'][y]
-    X = mfma16(B[s], Wi[s], X);
-  }
-  PK_GUARD_MFMA();
-  const f32x2 Xl = pk_lo(X), Xh = pk_hi(X);
-#endif
-  // constants in the result layout: M[4q + r][c] = M[c][4q + r] = Mc[r];  S[(4q + r) - c] = -Sc[r]
-  f32x2 p0 = pk_mul(Xl, K.Ml);
-  f32x2 px = pk_mul(pk_lo(G3), K.Ml);
-  f32x2 py = pk_mul(Xl, K.Sl);
-  pk_acc_fma(p0, Xh, K.Mh);
-  pk_acc_fma(px, pk_hi(G3), K.Mh);
-  pk_acc_fma(py, Xh, K.Sh);
-  const float s0 = p0.x + p0.y, tx = px.x + px.y, ty = py.x + py.y;
+  const f32x2 rl = pk_lo(Pr), rh = pk_hi(Pr), il = pk_lo(Pi), ih = pk_hi(Pi);
+  // rows (r, r + 2) are a pair:  (Pi[0] Pr[2] - Pi[2] Pr[0],  Pi[1] Pr[3] - Pi[3] Pr[1]) . (-2 t_{2q}, -2 t_{2q+1});
+  // columns (c, c ^ 2) are a pair: the lane's Pi against the partner's Pr, sign and t_k in the lane's constant.
+  // The three chains take turns (a result is two instructions old when it is read), and the DPP products sit inside
+  // the hand-kept group: one the compiler emits itself gets its own wait states for the matrix results on top of
+  // the guard's.
+  f32x2 p0 = pk_mul(rl, rl);
+  f32x2 py = pk_mul(il, rh);
+  float px = dpp4e_mul(Pr[0], Pi[0]);
+  pk_acc_fma(p0, rh, rh);
+  pk_acc_fnma(py, ih, rl);
+  dpp4e_fmac(px, Pr[1], Pi[1]);
+  pk_acc_fma(p0, il, il);
+  py = pk_mul(py, K.ky);
+  dpp4e_fmac(px, Pr[2], Pi[2]);
+  pk_acc_fma(p0, ih, ih);
+  dpp4e_fmac(px, Pr[3], Pi[3]);
+  __builtin_amdgcn_sched_barrier(0);
+  const float s0 = p0.x + p0.y, tx = px * K.kx, ty = py.x + py.y;
   // (the second operand of the second fold is a register that is dead by now: rows 2, 3 of that fold -- row 3 of z --
   // are never read, and a swap of ty with itself would need a copy first)
   float z = swap16_add(swap32_add(s0, tx), swap32_add(ty, p0.y));   // rows: s0, ty, tx, (unused)
@@ -1922,7 +1865,7 @@ __device__ __forceinline__ float spot_qf_moments(const SpotQf &K, const float (&
   return z;
 }
 // the two slopes of a sub-aperture from its moments (sum I, sum (X - 7.5) I / 2, -sum (Y - 7.5) I as
-// spot_qf_moments leaves them: the y moment comes whole out of the shared accumulator, the x moment halved)
+// spot_qf_moments leaves them: the factors and the sign are part of the table's constants)
 __device__ __forceinline__ void qf_slopes(const DevSys &sys, float s0, float tx, float ty, float &sx, float &sy) {
   if (s0 > 0.f) {
     const float inv = __builtin_amdgcn_rcpf(s0);        // 1 ulp; slopes are compared at 1e-4"
@@ -2628,8 +2571,8 @@ void k_frame_wave(DevSys sys, DevState st, int env_begin,
   SpotQf qfk;
   if constexpr (QF) {
     const float4 ka = reinterpret_cast<const float4 *>(sys.qf_tab)[2 * lane], kb = reinterpret_cast<const float4 *>(sys.qf_tab)[2 * lane + 1];
-    qfk.Ml = f32x2{ka.x, ka.y}; qfk.Mh = f32x2{ka.z, ka.w};
-    qfk.Sl = f32x2{kb.x, kb.y}; qfk.Sh = f32x2{kb.z, kb.w};
+    qfk.h = f32x4{ka.x, ka.y, ka.z, ka.w};
+    qfk.ky = f32x2{kb.x, kb.y}; qfk.kx = kb.z;
   }
   // shared loads: wave 0 / 1: the two 16-byte halves of the lane's tip-tilt pairs, wave 2 (and 3, a
   // duplicate that hits in the L1): the PSF operand of the lane, [t][64] x 16 B

@@ -57,13 +57,54 @@ def cog_quadratic_form_six(M, S, phase_rev, amp, dt, field=None):
     return 7.5 + 2 * (M * G3).sum(dtype=dt) / s0, 7.5 + (S * X).sum(dtype=dt) / s0, s0
 
 
+def four_product_basis(N=64, nf=16):
+    """H' [16, 16] and t [8] with M = H' H'^T and S = H' L H'^T, L = 2 x 2 blocks [[0, t_k], [-t_k, 0]] on the column
+    pairs (2k, 2k + 1): Phi = R Sigma V^T (rows cos, sin(theta_j x)), H = sqrt(2) V Sigma, T = R^T U R = Q L Q^T
+    (antisymmetric: i T is Hermitian, its eigenvectors a + i b for +t_k give the plane), H' = H Q.  Nothing is divided by
+    a singular value.  The basis is not unique; the library builds its own (csrc/aomarl_qf4_host.h)."""
+    j = np.arange(nf)
+    th = 2 * np.pi * (j + 0.5) / N
+    x = np.arange(16)
+    Phi = np.empty((2 * nf, 16))
+    Phi[0::2], Phi[1::2] = np.cos(np.outer(th, x)), np.sin(np.outer(th, x))
+    U = np.zeros((2 * nf, 2 * nf))
+    u = 0.5 + (j >> 1)
+    U[2 * j + 1, 2 * j], U[2 * j, 2 * j + 1] = u, -u
+    R, sig, Vt = np.linalg.svd(Phi, full_matrices=False)
+    H = np.sqrt(2.0) * Vt.T * sig
+    T = R.T @ U @ R
+    T = 0.5 * (T - T.T)
+    lam, vec = np.linalg.eigh(1j * T)
+    Q, t = np.empty((16, 16)), np.empty(8)
+    for k, i in enumerate(np.argsort(-lam)[:8]):                  # the eight positive eigenvalues, descending
+        a, b = vec[:, i].real, vec[:, i].imag                     # T a = t b, T b = -t a, |a| = |b|, a . b = 0
+        t[k], Q[:, 2 * k], Q[:, 2 * k + 1] = lam[i], np.sqrt(2.0) * b, np.sqrt(2.0) * a
+    return H @ Q, t
+
+
+def cog_four_products(H, t, phase_rev, amp, dt, field=None):
+    """The same moments from FOUR products (the kernel's form): with P = H'^T E H' (E H' for the real and the imaginary
+    part, then H'^T . of each)  sum I = |P|^2 and the first moments pair neighbouring columns / rows of P_r, P_i with
+    t_k (csrc/aomarl_kernels.hip: spot_qf_moments).  `H`, `t` as four_product_basis returns them."""
+    if field is None:
+        E = amp * np.exp(2j * np.pi * phase_rev)
+        field = E.real, E.imag
+    Er, Ei, H, t = field[0].astype(dt), field[1].astype(dt), H.astype(dt), t.astype(dt)
+    Pr, Pi = H.T @ (Er @ H), H.T @ (Ei @ H)
+    s0 = (Pr * Pr + Pi * Pi).sum(dtype=dt)
+    mx = 2 * (t[None, :] * (Pi[:, 0::2] * Pr[:, 1::2] - Pi[:, 1::2] * Pr[:, 0::2])).sum(dtype=dt)
+    my = 2 * (t[:, None] * (Pi[0::2, :] * Pr[1::2, :] - Pi[1::2, :] * Pr[0::2, :])).sum(dtype=dt)
+    return 7.5 + mx / s0, 7.5 + my / s0, s0
+
+
 def main():
     p = params.builtin("production_sh_40x40_8m_3layers")
     w = geometry.build_system(p).wfss[0]
     assert (w.Nfft, w.pdiam, w.npix, w.nrebin) == (64, 16, 16, 2)
     M, S = kernels()
     rng = np.random.default_rng(1)
-    worst64 = worst32 = worst64_6 = worst32_6 = 0.0
+    H4, t4 = four_product_basis()
+    worst64 = worst32 = worst64_6 = worst32_6 = worst64_4 = worst32_4 = 0.0
     for trial in range(200):
         amp = (rng.random((16, 16)) > (0.0 if trial % 2 else 0.2)).astype(float)
         tilt = np.add.outer(np.arange(16) * rng.normal() * 0.08, np.arange(16) * rng.normal() * 0.08)
@@ -77,13 +118,20 @@ def main():
         c6 = cog_quadratic_form_six(M, S, ph, amp, np.float32)
         worst64_6 = max(worst64_6, abs(a[0] - b6[0]), abs(a[1] - b6[1]))
         worst32_6 = max(worst32_6, abs(a[0] - c6[0]), abs(a[1] - c6[1]))
+        b4 = cog_four_products(H4, t4, ph, amp, np.float64)
+        c4 = cog_four_products(H4, t4, ph, amp, np.float32)
+        worst64_4 = max(worst64_4, abs(a[0] - b4[0]), abs(a[1] - b4[1]))
+        worst32_4 = max(worst32_4, abs(a[0] - c4[0]), abs(a[1] - c4[1]))
     print("200 random sub-apertures (half of them partly masked), pixels of %.4f arcsec:" % w.pixsize)
     print("  quadratic form in float64 vs FFT definition: max |d cog| = %.3g pixels" % worst64)
     print("  quadratic form in float32 vs FFT definition: max |d cog| = %.3g pixels" % worst32)
-    print("  six products (the kernel's form) in float64:   max |d cog| = %.3g pixels" % worst64_6)
-    print("  six products (the kernel's form) in float32:   max |d cog| = %.3g pixels" % worst32_6)
+    print("  six products (the kernel's form until round 8) in float64: max |d cog| = %.3g pixels" % worst64_6)
+    print("  six products (the kernel's form until round 8) in float32: max |d cog| = %.3g pixels" % worst32_6)
+    print("  four products (the kernel's form) in float64:  max |d cog| = %.3g pixels" % worst64_4)
+    print("  four products (the kernel's form) in float32:  max |d cog| = %.3g pixels" % worst32_4)
     assert worst64 < 1e-6 and worst32 < 2e-5
     assert worst64_6 < 1e-6 and worst32_6 < 2e-5
+    assert worst64_4 < 1e-6 and worst32_4 < 2e-5
 
 
 if __name__ == "__main__":
