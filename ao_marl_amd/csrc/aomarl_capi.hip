@@ -54,7 +54,7 @@ struct aomarl_ctx {
   hipEvent_t ev_reset = nullptr, ev_reset2[3] = {nullptr, nullptr, nullptr};
   bool no_extrude_sg = false;          // "extrude_unfused": scatter and gather of consecutive rounds as separate launches
   bool defer_dm_shape = false;         // composites: stack-array phase from st->voltage on the fly
-  int fused_debug = 0;                 // development switches of k_frame_fused (tools/fw_ab.py, tools/fw_pmc.py)
+  int fused_debug = 0;                 // development switches of k_frame_wave (tools/fw_ab.py, tools/fw_pmc.py)
   // "prefetch_atmos": the composite moves the atmosphere of the NEXT frame on a side stream as soon
   // as this frame's image kernels are done, so the extrusion chain runs beside do_control / the
   // agents / next_part_two instead of in front of the next image

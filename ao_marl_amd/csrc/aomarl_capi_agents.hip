@@ -73,15 +73,12 @@ __device__ __forceinline__ int af_at(int row, int col) {
   return (((col >> 4) * 64 + ((col >> 2) & 3) * 16 + row) << 2) + (col & 3);
 }
 
-#ifndef AF_D
-#define AF_D 2
-#endif
 // Out[16][N] = act(Xs[16][K] . W^T + b) on tiled images; ksteps = ceil(K / 16), W has ntile row tiles.
 __device__ __forceinline__ void af_layer(const float *__restrict__ Xs, int ksteps, const float *__restrict__ W,
                                          const float *__restrict__ b, int N, bool relu, float *__restrict__ Out) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, kk = lane >> 4;
   const int ntile = (N + 15) / 16, npairs = (ntile + 1) / 2;
-  constexpr int D = AF_D;
+  constexpr int D = 2;
   for (int pair = wave; pair < npairs; pair += 8) {
     const float4 *wa = reinterpret_cast<const float4 *>(W) + (long long)(2 * pair) * ksteps * 64 + lane;
     const float4 *wb = reinterpret_cast<const float4 *>(W) + (long long)min(2 * pair + 1, ntile - 1) * ksteps * 64 + lane;
@@ -146,7 +143,6 @@ __device__ __forceinline__ void af_layer(const float *__restrict__ Xs, int kstep
 }
 
 __global__ __launch_bounds__(512) void k_actor_fused(ActorArgs p) {
-  CHAIN_SETPRIO();
   extern __shared__ __attribute__((aligned(16))) float af_lds[];
   const int tiles = (p.nenv + 15) / 16;
   const int q = blockIdx.x & 7, idx = blockIdx.x >> 3;          // q: the XCD this workgroup lands on
@@ -213,7 +209,6 @@ struct StateBlocks {
 };
 
 __global__ void k_assemble_state(int nenv, StateBlocks sb, float *__restrict__ out) {
-  CHAIN_SETPRIO();
   const int e = blockIdx.y, j = blockIdx.x * blockDim.x + threadIdx.x;
   auto psum = [&](int col) {
     return sb.alpha * slab_sum<4>(sb.nsplit, [&](int z) { return sb.part[((long long)z * nenv + e) * sb.pn + col]; });

@@ -73,11 +73,6 @@ static bool next_round(const RoundOps &a, const RoundOps &b, RoundNext &nx) {
     if (at < 0) return false;
     nx.idx[at] = j; nx.dir[j] = b.dir[j]; nx.tflag[j] = b.tflag[j];
   }
-#ifdef SG_SAME_ONLY                              // (A/B builds: fuse only two rounds with the same operations, as before)
-  if (a.nops != b.nops) return false;
-  for (int i = 0; i < a.nops; i++)
-    if (a.layer[i] != b.layer[i] || a.dir[i] != b.dir[i] || a.tflag[i] != b.tflag[i]) return false;
-#endif
   return b.nops > 0;
 }
 

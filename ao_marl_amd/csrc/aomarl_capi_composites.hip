@@ -69,14 +69,9 @@ static int frame_fused_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, int f
   if (w.nblk != c->sys.ntiles) return fail("frame_fused: internal stripe count mismatch");
   const int nb = otf ? c->sys.otf_nb : 1;
   const bool hp = c->dft_mode < 0 ? g_precision != 0 : c->dft_mode == 1;
-  // twiddles + command lattice + the block's shared-data slots (two tiles x two parities with the pair walk) + one
-  // image of a tile pair's layer rows per wave (FW_DMA: the stack-array-from-voltages instantiations)
-  // ... + the moments of a stripe's sub-apertures per wave (the slopes-only fp32 instantiation: 16 bytes per tile)
-  const bool qf = FW_QF && otf && !hp && !noise && !cube;
-  const bool dma = FW_DMA && otf && (hp || FW_DMA_F32);
-  const size_t smm = sizeof(float) * ((qf ? 0 : 2 * 128) + (otf ? 4 * 4 * nb * c->sys.otf_latw : 0)) + FW_SLOT_BYTES(dma) +
-                     (dma ? 4 * FWD_WAVE(c->nlayers == 1 ? 1 : 3) : 128) +
-                     (qf ? 4 * 16 * (size_t)c->sys.ntiles : 0);
+  // the slopes-only fp32 instantiation (the kernel's QF); the LDS of a workgroup is laid out in frame_lds
+  const bool qf = otf && !hp && !noise && !cube;
+  const size_t smm = (size_t)frame_lds(qf, otf, c->nlayers == 1 ? 1 : 3, nb, c->sys.otf_latw, c->sys.ntiles).total;
   // Frames in flight beside the chains (frame pipeline, slot >= 0), slopes-only fp32 instantiation of a large system: the
   // workgroup asks for so much LDS that TWO of them fit a CU (3 x request > 160 KB) and what is left takes a workgroup of
   // the chains' products (46 KB) or of the actors (52.7 KB at 14 agents) at any time, instead of three frame workgroups

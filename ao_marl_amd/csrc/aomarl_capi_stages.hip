@@ -348,7 +348,6 @@ __global__ __launch_bounds__(256) void k_compose_rewards(int nm, const float *__
                                                          float *__restrict__ modes_out, int cx, int n_agents,
                                                          const int32_t *__restrict__ lohi, float factor,
                                                          float *__restrict__ rew) {
-  CHAIN_SETPRIO();
   const int r = blockIdx.y;
   if ((int)blockIdx.x >= cx) {
     if (threadIdx.x >= 64) return;

@@ -63,30 +63,6 @@ __device__ __forceinline__ f32x4d dn_mfma(float a, float b, f32x4d c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-// zero the one-pixel border of an [R][R][S] channel-last grid (S floats per position, S % 4 == 0,
-// or S == 1): 4R - 4 positions; the interior is overwritten by the layer that owns the grid (k_denoise4c;
-// the fp32 kernel reads the same positions from a table)
-template <int R, int S>
-__device__ __forceinline__ void dn_border4(float *p, int tid) {
-  constexpr int NP = 4 * R - 4;
-  if (S == 1) {
-    for (int i = tid; i < NP; i += 256) {
-      const int row = i < R ? 0 : (i < 2 * R ? R - 1 : 1 + ((i - 2 * R) >> 1));
-      const int col = i < R ? i : (i < 2 * R ? i - R : (((i - 2 * R) & 1) ? R - 1 : 0));
-      p[row * R + col] = 0.f;
-    }
-  } else {
-    constexpr int V = S / 4;
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = tid; i < NP * V; i += 256) {
-      const int pi = i / V, k = i - pi * V;
-      const int row = pi < R ? 0 : (pi < 2 * R ? R - 1 : 1 + ((pi - 2 * R) >> 1));
-      const int col = pi < R ? pi : (pi < 2 * R ? pi - R : (((pi - 2 * R) & 1) ? R - 1 : 0));
-      *reinterpret_cast<float4 *>(p + (row * R + col) * S + 4 * k) = z;
-    }
-  }
-}
-
 // four MFMAs: A = 4 consecutive channels of this lane's position, B = the matching weights
 __device__ __forceinline__ f32x4d dn_quad(const float4 a, const float4 b, f32x4d acc) {
   acc = dn_mfma(a.x, b.x, acc);

@@ -6,17 +6,6 @@
 
 #include "../../include/aomarl.h"
 
-// Wave priority of the control / agent chain's kernels against the frame kernel they share the SIMDs with: the issue
-// arbiter serves the oldest ready wave first, and the frame kernel's long-lived waves are always ready -- a chain
-// kernel's waves starve beside them (a 19 us product takes 160).  CHAIN_PRIO > 0 raises the chain's waves.
-#ifndef CHAIN_PRIO
-#define CHAIN_PRIO 0
-#endif
-#define CHAIN_SETPRIO() do { if (CHAIN_PRIO) __builtin_amdgcn_s_setprio(CHAIN_PRIO); } while (0)
-#ifndef ATM_PRIO
-#define ATM_PRIO 0
-#endif
-#define ATM_SETPRIO() do { if (ATM_PRIO) __builtin_amdgcn_s_setprio(ATM_PRIO); } while (0)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 // split-fp16 operand pairs (the opt-in fast mode): 2 / 8 halfs, and the matrix instruction they feed
@@ -191,13 +180,6 @@ __device__ __forceinline__ float philox_normal(uint32_t seed, uint32_t stream, u
   return (idx & 1) ? r * sinf(a) : r * cosf(a);
 }
 
-__device__ __forceinline__ float philox_uniform(uint32_t seed, uint32_t stream, uint32_t cnt_lo,
-                                                uint32_t cnt_hi, uint32_t idx) {
-  uint32_t x[4];
-  philox4x32_10(idx >> 2, cnt_lo, cnt_hi, stream, seed, 0x414F4D52u, x);
-  return u01(x[idx & 3]);
-}
-
 // ring-buffered screen: logical (x, y) -> physical float index.  Physical rows are
 // n + RING_PAD floats long: columns [n, n + RING_PAD) mirror columns [0, RING_PAD), so up to
 // RING_PAD consecutive logical pixels starting at a physical column < n are consecutive floats:
@@ -206,19 +188,31 @@ __device__ __forceinline__ float philox_uniform(uint32_t seed, uint32_t stream, 
 // pieces -- on the scalar unit); the extrusion scatter keeps the mirror up to date.
 // (56, not 32: with the screens of the production files -- 648 and 168 pixels -- the row pitch is then a multiple of
 // 128 bytes, every row of a tile starts at the same offset inside its line; see k_reset_env)
-#ifndef RING_PAD
 #define RING_PAD 56
-#endif
 static_assert(RING_PAD >= 32 && RING_PAD % 4 == 0, "the frame kernel's pair fetch reads 32 consecutive pixels in 16-byte pieces");
-#ifndef FW_ALIGN_ORIGIN
-#define FW_ALIGN_ORIGIN 1  // 0: a reset starts the rings at origin (0, 0)
-#endif
 __device__ __forceinline__ int ring_idx(int x, int y, int ox, int oy, int n) {
   int px = x + ox;
   px -= (px >= n) ? n : 0;
   int py = y + oy;
   py -= (py >= n) ? n : 0;
   return py * (n + RING_PAD) + px;
+}
+
+// Dynamic LDS of a k_frame_wave workgroup: byte offsets of its regions and their sum.  The kernel takes its pointers
+// from this, the host the size of the launch.
+//   0      [128] float2 WFS twiddles (none in the slopes-only fp32 instantiation, qf)
+//   lat    [4 waves][4 NB][latw] floats: the command lattice (stack-array DM from the voltages, otf)
+//   slots  the block's shared-data slots -- per-tile walk: [2][4][64] float4; pair walk: [2 parities][2 tiles][4][64]
+//   img    otf: [4 waves][NL] images of a tile pair's layer rows, FWD_IMG bytes each; otherwise 128 bytes of slack
+//   qmom   qf: [4 waves][ntl] float4 moments of the stripe's sub-apertures
+#define FWD_IMG (2 * 1024 + 128)           // bytes of a layer image
+struct FrameLds { int lat, slots, img, qmom, total; };
+__host__ __device__ constexpr FrameLds frame_lds(bool qf, bool otf, int NL, int NB, int latw, int ntl) {
+  const int lat = qf ? 0 : 128 * 8;
+  const int slots = lat + 4 * (4 * 4 * NB * (otf ? latw : 0));
+  const int img = slots + 16384;
+  const int qmom = img + (otf ? 4 * NL * FWD_IMG : 128);
+  return {lat, slots, img, qmom, qmom + (qf ? 4 * 16 * ntl : 0)};
 }
 
 // ---- cross-lane helpers on the VALU (DPP) instead of the LDS crossbar (ds_bpermute)

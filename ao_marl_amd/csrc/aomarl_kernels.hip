@@ -486,7 +486,6 @@ struct GemmEpi {
 
 __global__ void k_gemm_reduce_epi(int M, int N, int nsplit, float alpha, const float *__restrict__ P,
                                   float beta, float *__restrict__ C, int ldc, GemmEpi ep) {
-  CHAIN_SETPRIO();
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)M * N) return;
   const int row = (int)(i / N), col = (int)(i - (long long)row * N);
@@ -716,7 +715,6 @@ __device__ __forceinline__ void extrude_gather_item(const DevSys &sys, const Dev
 __global__ __launch_bounds__(256) void k_extrude_gather(DevSys sys, DevState st, int env_begin,
                                                         RoundOps ops, float *__restrict__ Z,
                                                         int ldz, float *__restrict__ ZREF) {
-  ATM_SETPRIO();
   const int col = blockIdx.x;
   const int e = env_begin + col / ops.nops, li = ops.layer[col % ops.nops];
   const int ox = st.origin[(e * sys.nlayers + li) * 2], oy = st.origin[(e * sys.nlayers + li) * 2 + 1];
@@ -780,7 +778,6 @@ __global__ __launch_bounds__(256) void k_extrude_scatter(DevSys sys, DevState st
                                                          const float *__restrict__ ZREF,
                                                          const float *__restrict__ P, int nsplit,
                                                          int ncol, int pn, float pscale) {
-  ATM_SETPRIO();
   const int col = blockIdx.x;
   const int e = env_begin + col / ops.nops, li = ops.layer[col % ops.nops];
   int *o = st.origin + (e * sys.nlayers + li) * 2;
@@ -803,13 +800,8 @@ __global__ __launch_bounds__(256) void k_extrude_scatter(DevSys sys, DevState st
 // directions: `nx` says where this column's layer sits in it; its Z / ZREF are a second pair of buffers
 // (ZN / ZREFN: the next round numbers its columns anew, another block may still need this round's ZREF entry).
 #define SG_MAX_N 1024                            // longest line k_extrude_sg keeps in LDS (checked on the host)
-#ifndef SG_EARLY
-#define SG_EARLY 1                               // 0 (A/B builds): every stencil value read back from the ring behind the barrier, as before round 6
-#endif
-#ifndef SG_THREADS
 #define SG_THREADS 512                           // threads per column; SG_U stencil items per thread: ns <= SG_U * SG_THREADS
 #define SG_U 4
-#endif
 __global__ __launch_bounds__(SG_THREADS) void k_extrude_sg(DevSys sys, DevState st, int env_begin, RoundOps ops,
                                                     const float *__restrict__ NEWL, int ldn,
                                                     const float *__restrict__ ZREF, const float *__restrict__ P,
@@ -817,7 +809,6 @@ __global__ __launch_bounds__(SG_THREADS) void k_extrude_sg(DevSys sys, DevState 
                                                     float *__restrict__ Z, int ldz, float *__restrict__ ZREFN,
                                                     RoundNext nx) {
   __shared__ float snew[SG_MAX_N];               // the line this block writes, for the next stencil's points on it
-  ATM_SETPRIO();
   const int col = blockIdx.x;
   const int el = col / ops.nops, oi = col % ops.nops;
   const int e = env_begin + el, li = ops.layer[oi];
@@ -868,15 +859,13 @@ __global__ __launch_bounds__(SG_THREADS) void k_extrude_sg(DevSys sys, DevState 
     const bool top_right = (dir == 1 || dir == -2);
     const int zx = top_right ? n - 1 : 0, zy = top_right ? 0 : n - 1;
     znew = on_new(zx, zy, zr);
-    if (SG_EARLY && !znew) zref = base[ring_idx(zx, zy, eox, eoy, n)];
+    if (!znew) zref = base[ring_idx(zx, zy, eox, eoy, n)];
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const int x = xy[u] & 0xFFFF, y = xy[u] >> 16;
       nw[u] = on_new(x, y, rr[u]);
-      if (SG_EARLY && !nw[u]) v[u] = base[ring_idx(x, y, eox, eoy, n)];
-      if (!SG_EARLY) rr[u] = ring_idx(x, y, eox, eoy, n);
+      if (!nw[u]) v[u] = base[ring_idx(x, y, eox, eoy, n)];
     }
-    if (!SG_EARLY) zr = ring_idx(zx, zy, eox, eoy, n);
     const uint32_t seed = st.seeds[e] + (uint32_t)li;
     for (int g = threadIdx.x; g < (n + 3) / 4; g += blockDim.x) {
       float z4[4];
@@ -895,16 +884,11 @@ __global__ __launch_bounds__(SG_THREADS) void k_extrude_sg(DevSys sys, DevState 
     st.ext_count[e * sys.nlayers + li] = cnt + 1u;
   }
   if (ni < 0) return;
-  if (SG_EARLY) {
-    if (znew) zref = snew[zr];
-  } else {
-    zref = base[zr];
-  }
+  if (znew) zref = snew[zr];
 #pragma unroll
   for (int u = 0; u < U; u++) {
     const int j = (int)threadIdx.x + u * (int)blockDim.x;
-    if (SG_EARLY) { if (nw[u]) v[u] = snew[rr[u]]; }
-    else v[u] = base[rr[u]];
+    if (nw[u]) v[u] = snew[rr[u]];
     if (j < ns) Z[(long long)col2 * ldz + j] = v[u] - zref;
   }
   if (threadIdx.x == 0) ZREFN[col2] = zref;
@@ -1075,16 +1059,12 @@ __global__ void k_reset_env(DevSys sys, DevState st, int env_begin, int env_coun
     st.frame[e] = 0u;
   }
   for (int i = threadIdx.x; i < sys.nlayers; i += blockDim.x) {
-#if FW_ALIGN_ORIGIN
     // Where the ring starts is free (the logical screen does not depend on it).  Start it so that the first pupil
     // pixel of a row sits on a 128-byte line once the reset is through: the frame kernel's 32-pixel pieces of a layer
     // that does not move along x (ground layers under a wind along y: this ring origin never changes) then ARE whole
     // lines, for the whole episode.  The reset's 2 dim extrusions bring the origin back to where it started, and its
     // final transposition exchanges x and y (origin_in_y: start the offset in y).
     const int a = sys.fused_ok ? (32 - (sys.layers[i].tox & 31)) & 31 : 0;
-#else
-    const int a = 0;
-#endif
     st.origin[(e * sys.nlayers + i) * 2] = origin_in_y ? 0 : a;
     st.origin[(e * sys.nlayers + i) * 2 + 1] = origin_in_y ? a : 0;
     st.ext_count[e * sys.nlayers + i] = 0u;
@@ -1265,15 +1245,6 @@ __global__ void k_get_dm_shape(DevSys sys, DevState st, int env_begin, int k, fl
 // =============================================================================================
 // raytrace into a phase buffer (generic, bilinear) -- unfused API path
 // =============================================================================================
-__device__ __forceinline__ float bilinear_plain(const float *in, int N, float fx, float fy) {
-  int ix = (int)floorf(fx), iy = (int)floorf(fy);
-  float wx = fx - (float)ix, wy = fy - (float)iy;
-  if (ix < 0 || iy < 0 || ix >= N || iy >= N) return 0.f;
-  int ix1 = ix + 1 < N ? ix + 1 : ix, iy1 = iy + 1 < N ? iy + 1 : iy;
-  float v00 = in[iy * N + ix], v01 = in[iy * N + ix1], v10 = in[iy1 * N + ix], v11 = in[iy1 * N + ix1];
-  return (1.f - wy) * ((1.f - wx) * v00 + wx * v01) + wy * ((1.f - wx) * v10 + wx * v11);
-}
-
 __device__ __forceinline__ float bilinear_ring(const float *in, int N, int ox, int oy, float fx,
                                                float fy) {
   int ix = (int)floorf(fx), iy = (int)floorf(fy);
@@ -1358,17 +1329,6 @@ __device__ __forceinline__ float poisson_draw(float lam, float u, float zn) {
   if (lam < 30.f) {
     // hardware exp2 / reciprocal (1 ulp): the cumulative sums move in their last bit against the
     // oracle's libm, which flips a count where u sits within ~1e-7 of a threshold
-#ifdef AOMARL_LIBM_NOISE
-    float p = expf(-lam), c = p;
-    int k = 0;
-    while (u > c && k < 200) {
-      k++;
-      p *= lam / (float)k;
-      const float cn = c + p;
-      if (cn == c) break;     // the sum has stopped growing below u: the tail is exhausted (see below)
-      c = cn;
-    }
-#else
     float p = __expf(-lam), c = p;
     int k = 0;
     // the fp32 cumulative sum levels off a few ulps below 1 (0.9999999 for lam = 1) while u01 reaches 1.0: for a u
@@ -1381,7 +1341,6 @@ __device__ __forceinline__ float poisson_draw(float lam, float u, float zn) {
       if (cn == c) break;
       c = cn;
     }
-#endif
     return (float)k;
   }
   float v = floorf(lam + sqrtf(lam) * zn + 0.5f);
@@ -1397,19 +1356,11 @@ __device__ __forceinline__ float sh_noise(float lam, float sigma, uint32_t seed,
   // Box-Muller on the transcendental unit: log2, and sin / cos of an angle given in revolutions
   // (v_sin_f32 / v_cos_f32 take exactly that) -- ~6 instructions against ~150 for libm's logf, sinf,
   // cosf; the normals agree with the oracle's to ~1e-6
-#ifdef AOMARL_LIBM_NOISE
-  const float r = sqrtf(-2.0f * logf(u01(x[1])));
-  const float a = 6.28318530717958647692f * u01(x[2]);
-  float v = poisson_draw(lam, u01(x[0]), r * cosf(a));
-  if (sigma > 0.f) v += sigma * (r * sinf(a));
-  return v;
-#else
   const float r = sqrtf(-2.0f * __logf(u01(x[1])));
   const float t = u01(x[2]);
   float v = poisson_draw(lam, u01(x[0]), r * __builtin_amdgcn_cosf(t));
   if (sigma > 0.f) v += sigma * (r * __builtin_amdgcn_sinf(t));
   return v;
-#endif
 }
 
 // MFMA stages + binning + normalisation (+noise) + COG of one sub-aperture whose complex amplitude
@@ -1623,41 +1574,15 @@ __device__ __forceinline__ void spot_cog_f32(const DevSys &sys, const DevState &
 // written before it in the source is issued before it) and an s_nop that covers the longest such distance.
 // All statements are `asm volatile`: they stay in source order among themselves.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-#ifdef FW_DBG_NONOP                              // (timing experiment: hazards unprotected, garbage results)
-#define PK_GUARD_MFMA() do { __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
 #define PK_GUARD_MFMA() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_nop 10"); } while (0)
-#endif
 #define PK_GUARD_TRANS() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_nop 1"); } while (0)
 // (a group's results feed matrix instructions: two wait states of margin, although gfx950 documents none)
 #define PK_END_TO_MFMA() do { asm volatile("s_nop 1"); __builtin_amdgcn_sched_barrier(0); } while (0)
 __device__ __forceinline__ f32x2 pk_lo(f32x4 v) { return __builtin_shufflevector(v, v, 0, 1); }
 __device__ __forceinline__ f32x2 pk_hi(f32x4 v) { return __builtin_shufflevector(v, v, 2, 3); }
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
-  f32x2 d;
-  asm volatile("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-// a * b - c
-__device__ __forceinline__ f32x2 pk_fma_nc(f32x2 a, f32x2 b, f32x2 c) {
-  f32x2 d;
-  asm volatile("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-// c - a * b
-__device__ __forceinline__ f32x2 pk_fma_na(f32x2 a, f32x2 b, f32x2 c) {
-  f32x2 d;
-  asm volatile("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
 __device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
   f32x2 d;
   asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-  return d;
-}
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-  f32x2 d;
-  asm volatile("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
   return d;
 }
 __device__ __forceinline__ f32x2 pk_mul(f32x2 a, f32x2 b) {
@@ -1665,7 +1590,6 @@ __device__ __forceinline__ f32x2 pk_mul(f32x2 a, f32x2 b) {
   asm volatile("v_pk_mul_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
   return d;
 }
-__device__ __forceinline__ f32x4 pk_join(f32x2 lo, f32x2 hi) { return __builtin_shufflevector(lo, hi, 0, 1, 2, 3); }
 // in-place forms for accumulators that live across branches / loop iterations (an "=v" result is a new register: the
 // compiler then copies it back where control flow joins) and forms whose constant operand stays in a scalar register
 // pair (a loop-invariant pair in vector registers is re-materialised from its scalars every iteration: one
@@ -1690,78 +1614,6 @@ __device__ __forceinline__ f32x2 pk_mul_s(f32x2 a, f32x2 bs) {
   f32x2 d;
   asm volatile("v_pk_mul_f32 %0, %1, %2" : "=v"(d) : "v"(a), "s"(bs));
   return d;
-}
-
-// spot_cog_f32 with its vector arithmetic packed (same formulas, the sums in pairs): 8 + 24 packed instructions for
-// the stage-1 combinations and the P / D sums instead of 16 + 48 scalar ones.
-__device__ __forceinline__ void spot_cog_f32_pk(const DevSys &sys, const DevState &st, int e, int i, int lane,
-                                                const float (&Cc)[4], const float (&Ss)[4], const float (&br)[4],
-                                                const float (&bi)[4], int do_cog, const f32x4 z4) {
-  const int q = lane >> 4, c = lane & 15;
-  // ---- stage 1 (y = c on M, x = 4q + s on K, k = c on N)
-  f32x4 PCr = z4, PCi = z4, PSr = z4, PSi = z4;
-#pragma unroll
-  for (int s = 0; s < 4; s++) {
-    PCr = mfma16(br[s], Cc[s], PCr);
-    PCi = mfma16(bi[s], Cc[s], PCi);
-    PSr = mfma16(br[s], Ss[s], PSr);
-    PSi = mfma16(bi[s], Ss[s], PSi);
-  }
-  // [0]: kx = +(k+1/2): (PCr + PSi, PCi - PSr)   [1]: kx = -(k+1/2): (PCr - PSi, PCi + PSr)
-  PK_GUARD_MFMA();
-  const f32x2 tr0l = pk_add(pk_lo(PCr), pk_lo(PSi)), ti0l = pk_sub(pk_lo(PCi), pk_lo(PSr));
-  const f32x2 tr0h = pk_add(pk_hi(PCr), pk_hi(PSi)), ti0h = pk_sub(pk_hi(PCi), pk_hi(PSr));
-  const f32x2 tr1l = pk_sub(pk_lo(PCr), pk_lo(PSi)), ti1l = pk_add(pk_lo(PCi), pk_lo(PSr));
-  const f32x2 tr1h = pk_sub(pk_hi(PCr), pk_hi(PSi)), ti1h = pk_add(pk_hi(PCi), pk_hi(PSr));
-  PK_END_TO_MFMA();
-  const f32x4 TrA[2] = {pk_join(tr0l, tr0h), pk_join(tr1l, tr1h)};
-  const f32x4 TiA[2] = {pk_join(ti0l, ti0h), pk_join(ti1l, ti1h)};
-  f32x2 Pa[2], Pb[2];                            // P of half m in two partial pairs
-  f32x2 Da, Db;                                  // D over registers (0, 1) and (2, 3), both halves
-#pragma unroll
-  for (int m = 0; m < 2; m++) {
-    const f32x4 Tr = TrA[m], Ti = TiA[m];
-    f32x4 QCr = z4, QCi = z4, QSr = z4, QSi = z4;
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-      QCr = mfma16(Cc[s], Tr[s], QCr);
-      QCi = mfma16(Cc[s], Ti[s], QCi);
-      QSr = mfma16(Ss[s], Tr[s], QSr);
-      QSi = mfma16(Ss[s], Ti[s], QSi);
-    }
-    PK_GUARD_MFMA();
-    const f32x2 crl = pk_lo(QCr), crh = pk_hi(QCr), cil = pk_lo(QCi), cih = pk_hi(QCi);
-    const f32x2 srl = pk_lo(QSr), srh = pk_hi(QSr), sil = pk_lo(QSi), sih = pk_hi(QSi);
-    f32x2 pa = pk_mul(crl, crl), pb = pk_mul(crh, crh);
-    if (m == 0) { Da = pk_mul(crl, sil); Db = pk_mul(crh, sih); }
-    else { pk_acc_fma(Da, crl, sil); pk_acc_fma(Db, crh, sih); }
-    pk_acc_fma(pa, sil, sil); pk_acc_fma(pb, sih, sih);
-    pk_acc_fnma(Da, cil, srl); pk_acc_fnma(Db, cih, srh);
-    pk_acc_fma(pa, cil, cil); pk_acc_fma(pb, cih, cih);
-    pk_acc_fma(pa, srl, srl); pk_acc_fma(pb, srh, srh);
-    Pa[m] = pa; Pb[m] = pb;
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  const f32x2 P0 = pk_add(Pa[0], Pb[0]), P1 = pk_add(Pa[1], Pb[1]);
-  const float Xp = (float)(8 + (c >> 1)), Xm = (float)(7 - (c >> 1));
-  const float p0 = P0.x + P0.y, p1 = P1.x + P1.y, da = Da.x + Da.y, db = Db.x + Db.y;
-  float s0 = p0 + p1;
-  float sx = fmaf(Xm, p1, Xp * p0);
-  float sy = fmaf((float)(3 + 4 * q), db, fmaf((float)(1 + 4 * q), da, 7.5f * s0));
-  s0 = wave_sum_last(s0);
-  sx = wave_sum_last(sx);
-  sy = wave_sum_last(sy);
-  if (do_cog && lane == 63) {
-    float *sl = st.slopes + (long long)e * sys.nslope;
-    if (s0 > 0.f) {
-      const float inv = __builtin_amdgcn_rcpf(s0);       // 1 ulp; slopes are compared at 1e-4"
-      sl[i] = (sx * inv - sys.cog_offset) * sys.cog_scale;
-      sl[sys.nvalid + i] = (sy * inv - sys.cog_offset) * sys.cog_scale;
-    } else {
-      sl[i] = 0.f;
-      sl[sys.nvalid + i] = 0.f;
-    }
-  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2476,38 +2328,9 @@ struct FrameRaw {
 // once at its end:  kx = +k: (PA_C + PB_S, PB_C - PA_S);  kx = -k: (PA_C - PB_S, PB_C + PA_S).  The
 // kx = 0 column is the plain row sum of the amplitudes: 8 vector adds per tile.
 template <int NL, int NB, bool OTF, bool NOISE, bool WRITE_CUBE, bool HP>
-// 3 waves per SIMD (<= 168 VGPRs).  Forcing the fp32 slopes-only instantiation (140 VGPRs) into four (<= 128, 8
-// registers spilled) measured 0.466 against 0.459 ms: the kernel is bound by issue slots, not by latency
-#ifndef FW_WAVES
-#define FW_WAVES 3
-#endif
-#ifndef FW_QF
-#define FW_QF 1            // 0: the slopes-only fp32 instantiation goes through the pruned transform (spot_cog_f32_pk)
-#endif
-#ifndef FW_DMA
-#define FW_DMA 1           // 0: layer rows fetched per tile into vector registers (16 rows x 64 B per instruction)
-#endif
-#ifndef FW_DEPTH
-#define FW_DEPTH 2         // lit tiles of loads in flight per wave in the per-tile walk (register sets)
-#endif
-#ifndef FW_DMA_F32
-#define FW_DMA_F32 1       // 0: the pair walk for the split-fp16 instantiations only
-#endif
-// Round 6 experiment (FW_SLOTS1 = 1; built, measured, NOT the default): the pair walk's shared-data slots single-buffered,
-// three quarters per tile (2 x 3 KB instead of 2 x 2 x 4 KB; with no twiddle table in the slopes-only instantiation:
-// 37.5 KB of LDS per workgroup instead of 49).  Three frame workgroups then leave 46 KB of a CU's 160, and one workgroup
-// of the chains' products (k_gemm_p<2, 3>: 46 080 B, 156 registers beside 3 x 112) is resident beside them on EVERY CU
-// instead of starting when a frame workgroup retires.  Price: the slots are read into registers between two barriers.
-// Measured (alternating runs on one box, gpurun_out/r06f_*, r06g_*): the frame kernel in the loop gets FASTER (0.365
-// against 0.386 ms: it always has its three workgroups) and the step SLOWER (0.494 against 0.482 ms, 512 against 524 k):
-// a product's wave beside three frame waves gets a quarter of the SIMD's issue slots, one that took a retired frame
-// workgroup's place a third -- and the step waits for the products' chain, not for the frame kernel.  Wave priorities on
-// top (GP_PRIO / ATM_PRIO / CHAIN_PRIO) change nothing, in either layout.
-#ifndef FW_SLOTS1
-#define FW_SLOTS1 0
-#endif
-#define FW_SLOT_BYTES(dma) ((dma) ? (FW_SLOTS1 ? 2 * 3 * 1024 : 16384) : 16384)
-// Layer rows of a PAIR of adjacent tiles as whole 128-byte pieces, straight into LDS (FW_DMA, the stack-array-from-
+// 3 waves per SIMD (<= 168 VGPRs): the kernel is bound by issue slots, not by latency -- a fourth wave (<= 128
+// registers, 8 of them spilled) made it slower
+// Layer rows of a PAIR of adjacent tiles as whole 128-byte pieces, straight into LDS (the stack-array-from-
 // voltages instantiations).  A load instruction that covers 16 rows x 64 B (the compute layout: lane (q, c) = row c,
 // pixels 4q .. 4q + 3) makes the memory pipeline handle every 128-byte line twice, half a line at a time; as
 // 8 rows x 128 contiguous bytes the same bytes arrive 25 % faster (tools/dmabench.hip: 3.9 -> 4.9 TB/s on this access
@@ -2517,10 +2340,8 @@ template <int NL, int NB, bool OTF, bool NOISE, bool WRITE_CUBE, bool HP>
 // 8 rows x 8 chunks of 16 bytes in LANE order (what that instruction can write), the second block 128 bytes further,
 // the chunk a lane fetches XOR-ed with its row (lane = 8 row + (chunk ^ row)): the compute layout's ds_read_b128
 // (row c, chunk 4 h + q of tile h) then finds its 16 lanes in 16 different bank groups.
-#define FWD_BLK 1152                       // bytes from block 0 to block 1 of a layer image
-#define FWD_IMG (2 * 1024 + 128)           // bytes of a layer image
-#define FWD_WAVE(nl) ((nl) * FWD_IMG)      // bytes per wave
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FW_WAVES, FW_WAVES)))
+#define FWD_BLK 1152                       // bytes from block 0 to block 1 of a layer image (FWD_IMG bytes: aomarl_dev.h)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void k_frame_wave(DevSys sys, DevState st, int env_begin,
                                                     int env_count, int do_cog,
                                                     float *__restrict__ TR,
@@ -2531,16 +2352,17 @@ void k_frame_wave(DevSys sys, DevState st, int env_begin,
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   // slopes only, fp32: the moments as quadratic forms of the field (spot_qf_moments): no transform, no Cc / Ss, no
   // twiddle table -- the lane's constants come from sys.qf_tab
-  constexpr bool QF = FW_QF && OTF && !HP && !NOISE && !WRITE_CUBE;
-  constexpr bool DMA = FW_DMA && OTF && (HP || FW_DMA_F32);
-  float2 *sTw = reinterpret_cast<float2 *>(smem);            // [128] WFS twiddles (none in the slopes-only instantiation)
-  float *lat_all = reinterpret_cast<float *>(sTw + (QF ? 0 : 128));     // [4 waves][4 NB][latw]
-  // per tile walk: [2][4][64]; pair walk: [2 tiles][3 quarters][64] (FW_SLOTS1) or [2 parities][2 tiles][4][64]
-  float4 *shb = reinterpret_cast<float4 *>(lat_all + 4 * 4 * NB * (OTF ? sys.otf_latw : 0));
-  char *dimg = reinterpret_cast<char *>(shb) + FW_SLOT_BYTES(DMA) + (DMA ? wv * FWD_WAVE(NL) : 0);   // this wave's layer images
+  constexpr bool QF = OTF && !HP && !NOISE && !WRITE_CUBE;
+  constexpr bool DMA = OTF;                                  // the pair walk
+  const FrameLds lds = frame_lds(QF, OTF, NL, NB, sys.otf_latw, ntl);
+  char *const lds0 = reinterpret_cast<char *>(smem);
+  float2 *sTw = reinterpret_cast<float2 *>(lds0);                // [128] WFS twiddles (none in the slopes-only instantiation)
+  float *lat_all = reinterpret_cast<float *>(lds0 + lds.lat);    // [4 waves][4 NB][latw]
+  float4 *shb = reinterpret_cast<float4 *>(lds0 + lds.slots);    // the block's shared-data slots
+  char *dimg = lds0 + lds.img + (DMA ? wv * NL * FWD_IMG : 0);   // this wave's layer images
   // slopes-only fp32 instantiation: the moments of the stripe's sub-apertures, [tile][s0, ty, tx, -] per wave,
   // turned into slopes once per stripe by lane = tile (the per-tile finish was a dozen instructions on ONE lane)
-  float4 *qmom = reinterpret_cast<float4 *>(reinterpret_cast<char *>(shb) + FW_SLOT_BYTES(DMA) + (DMA ? 4 * FWD_WAVE(NL) : 0)) + wv * ntl;
+  float4 *qmom = reinterpret_cast<float4 *>(lds0 + lds.qmom) + wv * ntl;
   const int dbg = do_cog >> 8;                               // development switches (kbench)
   do_cog &= 1;
   // blocks are dispatched x-fastest: x = group of 4 environments, y = rank of the stripe by
@@ -2743,16 +2565,12 @@ void k_frame_wave(DevSys sys, DevState st, int env_begin,
     if constexpr (!DM) {
       nlit++;
       slot[wv * 64 + lane] = make_float4(cur.SH.v[0], cur.SH.v[1], cur.SH.v[2], cur.SH.v[3]);
-#ifndef FW_DBG_NOBAR                             // (timing experiment: garbage results)
       __syncthreads();
-#endif
     }
-    if (!(DM && FW_SLOTS1)) {                      // (pair walk with single-buffered slots: the caller has read them)
-      const float4 t0 = slot[lane], t1 = slot[64 + lane];
-      cur.T[0] = t0.x; cur.T[1] = t0.y; cur.T[2] = t0.z; cur.T[3] = t0.w;
-      cur.T[4] = t1.x; cur.T[5] = t1.y; cur.T[6] = t1.z; cur.T[7] = t1.w;
-      cur.CS = slot[128 + lane];
-    }
+    const float4 t0 = slot[lane], t1 = slot[64 + lane];
+    cur.T[0] = t0.x; cur.T[1] = t0.y; cur.T[2] = t0.z; cur.T[3] = t0.w;
+    cur.T[4] = t1.x; cur.T[5] = t1.y; cur.T[6] = t1.z; cur.T[7] = t1.w;
+    cur.CS = slot[128 + lane];
     const float4 csP = cur.CS;                     // HP: [hi | lo] halfs; fp32: the 4 K steps
     // (a wave without an environment of its own -- env_count not a multiple of 4 -- repeats the block's last
     // one: same loads, same arithmetic, same values stored twice.  No branch on `active` in here: a join behind
@@ -2885,18 +2703,13 @@ void k_frame_wave(DevSys sys, DevState st, int env_begin,
         if constexpr (QF) {
           const float z = spot_qf_moments(qfk, wr, wi, Z4);
           if (c == 0 && q < 3) reinterpret_cast<float *>(qmom + t)[q] = z;     // lanes 0, 16, 32: the three row totals
-        } else if constexpr (PK) spot_cog_f32_pk(sys, st, e, info & 0xFFFF, lane, Cc, Ss, wr, wi, do_cog, Z4);
-        else spot_cog_f32(sys, st, e, info & 0xFFFF, lane, Cc, Ss, wr, wi, do_cog, Z4);
+        } else spot_cog_f32(sys, st, e, info & 0xFFFF, lane, Cc, Ss, wr, wi, do_cog, Z4);
       } else {
         spot_core<NOISE, WRITE_CUBE>(sys, st, e, info & 0xFFFF, lane, Cc, Ss, wr, wi, do_cog, flux_i, Z4);
       }
     }
   };
 
-  // The stripe's lit tiles, compact (sys.lit_info[r][k], tile index in bits 24..30; the entries past
-  // the last one repeat it, so the prefetch at the end of the list needs no test: the last tile is
-  // loaded again, from L2, and dropped).  TWO tiles of loads are in flight (two register sets, list
-  // walked in pairs; an odd first tile goes on its own).  The list is read with scalar loads.
   if constexpr (DMA) {
     // ---- the stripe's lit tiles in PAIRS (sys.pair_info): per pair ONE wait for everything fetched a pair ago, the
     // layer rows out of the wave's LDS image into registers, the block's shared data of both tiles into its slots,
@@ -2932,19 +2745,12 @@ void k_frame_wave(DevSys sys, DevState st, int env_begin,
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
                    : "=&s"(keep) : "v"(vo), "s"(rs), "s"(lds_addr), "s"(so) : "memory");
     };
-    // the block's shared data of a pair, one quarter per wave, filled in place (par: parity of the pair with
-    // double-buffered slots; single-buffered: three quarters per tile, wave 3 -- whose quarter was a duplicate -- idles)
+    // the block's shared data of a pair, one quarter per wave, filled in place (par: parity of the pair, the slots
+    // are double-buffered)
     auto issue_shared = [&](int ia, int ib, int par) {
       const int ta = (ia >> 24) & 0x7F, tb = (ib >> 24) & 0x7F;
-      if (FW_SLOTS1) {
-        if (wv < 3) {
-          dma16(shvo, shrs, shb_lds, (unsigned)ta << shstep);
-          dma16(shvo, shrs, shb_lds + 3072u, (unsigned)tb << shstep);
-        }
-      } else {
-        dma16(shvo, shrs, shb_lds + (unsigned)par * 8192u, (unsigned)ta << shstep);
-        dma16(shvo, shrs, shb_lds + (unsigned)par * 8192u + 4096u, (unsigned)tb << shstep);
-      }
+      dma16(shvo, shrs, shb_lds + (unsigned)par * 8192u, (unsigned)ta << shstep);
+      dma16(shvo, shrs, shb_lds + (unsigned)par * 8192u + 4096u, (unsigned)tb << shstep);
     };
     auto issue = [&](int ia, int ib) {
       const int ta = (ia >> 24) & 0x7F, tb = (ib >> 24) & 0x7F;
@@ -2974,46 +2780,24 @@ void k_frame_wave(DevSys sys, DevState st, int env_begin,
       }
       A.mrow = mrA; A.F = fA; B.mrow = mrB; B.F = fB;
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the image has been read: the next pair may overwrite it
-      if (FW_SLOTS1) {
-        if (k + 1 < np) issue(ja, jb);                         // (the wave's own images, masks, flux: nobody else reads them)
-        __syncthreads();                                       // every wave's quarters of THIS pair have landed
-        float4 *slots = shb;
-        {
-          const float4 a0 = slots[lane], a1 = slots[64 + lane];
-          A.CS = slots[128 + lane];
-          A.T[0] = a0.x; A.T[1] = a0.y; A.T[2] = a0.z; A.T[3] = a0.w; A.T[4] = a1.x; A.T[5] = a1.y; A.T[6] = a1.z; A.T[7] = a1.w;
-        }
-        if (ia & FW_LIT) tile(ia, 0, A, A, dm, slots);
-        {   // (the second tile's slot only now: twelve registers less across the first tile -- the kernel has to stay at
-            //  112, the product's workgroup beside three of its waves needs the other 160 of the SIMD's 512)
-          const float4 b0 = slots[192 + lane], b1 = slots[256 + lane];
-          B.CS = slots[320 + lane];
-          B.T[0] = b0.x; B.T[1] = b0.y; B.T[2] = b0.z; B.T[3] = b0.w; B.T[4] = b1.x; B.T[5] = b1.y; B.T[6] = b1.z; B.T[7] = b1.w;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __syncthreads();                                       // ... and everybody has read them: the next pair's may land
-        if (k + 1 < np) issue_shared(ja, jb, 0);
-        if (ib & FW_LIT) tile(ib, 0, B, B, dm, slots);
-      } else {
-        float4 *slots = shb + (k & 1) * 512;
-        __syncthreads();
-        if (k + 1 < np) { issue_shared(ja, jb, (k + 1) & 1); issue(ja, jb); }
-        if (ia & FW_LIT) tile(ia, 0, A, A, dm, slots);
-        if (ib & FW_LIT) tile(ib, 0, B, B, dm, slots + 256);
-      }
+      float4 *slots = shb + (k & 1) * 512;
+      __syncthreads();
+      if (k + 1 < np) { issue_shared(ja, jb, (k + 1) & 1); issue(ja, jb); }
+      if (ia & FW_LIT) tile(ia, 0, A, A, dm, slots);
+      if (ib & FW_LIT) tile(ib, 0, B, B, dm, slots + 256);
       ia = ja; ib = jb;
     }
   } else {
   // The stripe's lit tiles, compact (sys.lit_info[r][k], tile index in bits 24..30; the entries past the last one
   // repeat it, so the prefetches at the end of the list need no test: the last tile is loaded again, from L2, and
-  // dropped).  FW_DEPTH tiles of loads are in flight (as many register sets, the list walked in groups of that
+  // dropped).  D = 2 tiles of loads are in flight (as many register sets, the list walked in groups of that
   // many; the tiles left over come last, on data the last group prefetched).  The list is read with scalar loads.
   const std::integral_constant<int, 0> nd;
   const std::integral_constant<int, 2> nf;
   const int nl = sys.lit_count[r];
   const const_int_p linfo = (const_int_p)(unsigned long long)(sys.lit_info + r * (ntl + 8));
   {
-    constexpr int D = FW_DEPTH;
+    constexpr int D = 2;
     FrameRaw<NL, OTF> raw[D];
     int inf[D];
 #pragma unroll
@@ -3197,7 +2981,6 @@ __global__ void k_delay_sum(DevState st, int nactu, int ld, float a, float b, fl
 // behind the m2v product.  P: split-K partial tiles of that product (nsplit > 0) or null (st.com holds it).
 __global__ void k_delay_ahead(DevSys sys, DevState st, int nactu, int ld, int n, const float *__restrict__ P,
                               int nsplit, float alpha, int ktt) {
-  CHAIN_SETPRIO();
   auto newest = [&](int row, int a) -> float {
     if (nsplit > 0) {
       return alpha * slab_sum<4>(nsplit, [&](int z) { return P[((long long)z * n + row) * nactu + a]; });
@@ -3896,7 +3679,6 @@ __global__ __launch_bounds__(256) void k_strehl_commit(DevSys sys, DevState st, 
 __global__ __launch_bounds__(256) void k_post_delay(DevSys sys, DevState st, int env_begin, int n,
                                                     const float *__restrict__ PEND, int do_strehl, int ktt,
                                                     const float *__restrict__ volts, int ldv) {
-  CHAIN_SETPRIO();
   if ((int)blockIdx.x < n) {
     if (do_strehl) strehl_commit_body(sys, st, env_begin, blockIdx.x, PEND);
   } else {
