@@ -13,7 +13,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 # AOMARL_LIB: another build of the same library (A/B measurements of kernel variants, csrc/Makefile `variant`)
 LIB_PATH = os.environ.get("AOMARL_LIB") or os.path.join(HERE, "libaomarl_hip.so")
-MAX_LAYERS, MAX_DMS, ABI_VERSION = 8, 4, 2
+MAX_LAYERS, MAX_DMS, ABI_VERSION = 8, 4, 3
 PRECISION_F32, PRECISION_SPLIT_F16 = 0, 1
 
 DM_PZT, DM_TT = 0, 1
@@ -169,6 +169,11 @@ SYMBOLS = [
     ("aomarl_roket_moments", _i, [_vp, _vp, _vp, C.POINTER(C.c_longlong), _vp]),
     ("aomarl_roket_reset", _i, [_vp]),
     ("aomarl_roket_history", _i, [_vp, _vp, _vp, _vp]),
+    ("aomarl_psfrec_create", _i, [_vp, C.POINTER(C.c_void_p)]),
+    ("aomarl_psfrec_destroy", _i, [_vp]),
+    ("aomarl_psfrec_accumulate", _i, [_vp, _vp, _vp, _i, _vp]),
+    ("aomarl_psfrec_finish", _i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    ("aomarl_psfrec_reset", _i, [_vp]),
     ("aomarl_target_psf_buffer", _i, _range + [_vp]),
     ("aomarl_set_geo", _i, [_vp, _fp]),
     ("aomarl_geo_workspace_floats", C.c_size_t, [_vp, _i]),
@@ -239,6 +244,13 @@ class RoketDesc(C.Structure):
     """aomarl_roket_desc (include/aomarl.h)"""
     _fields_ = [(n, C.c_int32) for n in ("nenv", "nactu", "ld_actu", "nmodes", "nfiltered", "delay")] + \
                [("g", C.c_float), ("gamma", C.c_float), ("RD", _fp), ("P", _fp), ("Btt", _fp)]
+
+
+class PsfRecDesc(C.Structure):
+    """aomarl_psfrec_desc (include/aomarl.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("p", "N", "npts", "nactu", "ld_actu")] + \
+               [("lit", _ip), ("if_data", _fp), ("if_indices", _ip), ("if_indptr", _ip), ("tt", _fp),
+                ("denmask", _fp), ("mask", _fp), ("otftel", _fp)]
 
 
 class AomarlError(RuntimeError):

@@ -414,19 +414,26 @@ class VecRoket(object):
     def save(self, path, envs=None):
         """An .npz per call with the reference's key names (save_in_hdf5, :402-436), histories [nactu][frames behind
         the preloop] with a leading axis over `envs` (a subset of keep_envs; default: all of them)."""
+        d = self.to_dict(envs)
+        np.savez(path, **d)
+        return sorted(d)
+
+    def to_dict(self, envs=None):
+        """What save() writes, as a dictionary (psf_rec reads either)."""
         envs = list(self.keep_envs if envs is None else envs)
         if not envs or any(e not in self.keep_envs for e in envs):
             raise ValueError("save: envs=%r: histories were kept for keep_envs=%r only" % (envs, self.keep_envs))
         idx = [self.keep_envs.index(e) for e in envs]
-        d = npz_dict(self.hist, idx, envs, self.n_preloop, self.results(), self.sup.cal, self.cmat_h,
-                     None if self.psf_ortho is None else (self.psf_ortho / max(self._n_behind, 1)).cpu().numpy())
-        np.savez(path, **d)
-        return sorted(d)
+        return npz_dict(self.hist, idx, envs, self.n_preloop, self.results(), self.sup.cal, self.cmat_h,
+                        None if self.psf_ortho is None else (self.psf_ortho / max(self._n_behind, 1)).cpu().numpy(),
+                        spup=self.sup.s.spupil, tar_lambda=self.sup.s.tar_lambda, psf_ortho_envs=self.psf_ortho_envs)
 
 
-def npz_dict(hist, idx, envs, n_preloop, res, cal, cmat, psf_ortho=None):
+def npz_dict(hist, idx, envs, n_preloop, res, cal, cmat, psf_ortho=None, spup=None, tar_lambda=None, psf_ortho_envs=None):
     """The dictionary save() writes.  hist: per-frame lists, "x" [7][kept][nactu] and "com", "slopes", "wf_com",
-    "alias_meas", "trunc_meas" [kept][.]; idx: positions of `envs` among the kept environments."""
+    "alias_meas", "trunc_meas" [kept][.]; idx: positions of `envs` among the kept environments.  spup (the reference's
+    name, drax.get_pup) and tar_lambda (its attribute _Param_target__Lambda) are what the PSF reconstruction reads
+    beside the histories (psf_rec.py); psfortho_envs: the environments psfortho's leading axis runs over."""
     x = np.stack(hist["x"])[n_preloop:]                                # [frames][7][kept][nactu]
     h = lambda k: np.stack(hist[k])[n_preloop:][:, idx].transpose(1, 2, 0)       # noqa: E731
     xk = lambda k: x[:, k][:, idx].transpose(1, 2, 0)                  # noqa: E731
@@ -444,6 +451,12 @@ def npz_dict(hist, idx, envs, n_preloop, res, cal, cmat, psf_ortho=None):
          "alias_meas": h("alias_meas"), "trunc_meas": h("trunc_meas"), "envs": np.asarray(envs)}
     if psf_ortho is not None:
         d["psfortho"] = psf_ortho
+        if psf_ortho_envs is not None:
+            d["psfortho_envs"] = np.asarray(psf_ortho_envs)
+    if spup is not None:
+        d["spup"] = np.asarray(spup, dtype=np.float32)
+    if tar_lambda is not None:
+        d["tar_lambda"] = np.asarray([tar_lambda], dtype=np.float64)
     return d
 
 

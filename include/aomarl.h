@@ -26,7 +26,7 @@ extern "C" {
 
 #define AOMARL_MAX_LAYERS 8
 #define AOMARL_MAX_DMS 4
-#define AOMARL_ABI_VERSION 2
+#define AOMARL_ABI_VERSION 3
 
 enum { AOMARL_DM_PZT = 0, AOMARL_DM_TT = 1 };
 
@@ -672,6 +672,46 @@ int aomarl_roket_reset(aomarl_roket *r);
 /* x_out: DEVICE [7][nenv][nactu], the contributors of the last frame; bufs_out: DEVICE [4][nenv][nactu], its
  * noise_buf, trunc_buf, tomo_buf, mod_com.  Either may be NULL. */
 int aomarl_roket_history(aomarl_roket *r, float *x_out, float *bufs_out, void *stream);
+/* PSF reconstruction from the covariance of the ROKET error buffers, the Vii algorithm (guardians/gamora.py:24-100
+ * psf_rec_Vii, :103-171 psf_rec_vii_cpu).  For the eigenpairs (e_k, V_k) of the modal covariance and the phase maps
+ * m_k = IF^T (Btt V_k)[:-2] + TT (Btt V_k)[-2:] on the lit pixels of a p x p pupil, zero-padded to N x N (:148-159):
+ *     tmp  = Re( fft2(sum_k e_k m_k^2) . conj(fft2 pup) ) - sum_k e_k |fft2 m_k|^2     (the first term is linear in m_k^2)
+ *     dphi = Re ifft2(2 tmp) . den . mask . (2 pi / lambda)^2                             (:163)
+ *     otf2 = exp(-dphi / 2) . mask / max                                                  (:164-165)
+ *     psf  = fftshift Re ifft2(otf_other . otf2) . N^2 / npts                             (:167-168, :85-94)
+ * The object keeps var = sum_k e_k m_k^2 on the lit pixels and acc = sum_k e_k |fft2 m_k|^2 on N/2 + 1 columns.
+ * All HOST arrays of the desc are copied.
+ *   p, N, npts          pupil side, transform size (a power of two, 32..2048, N >= 2 p), number of lit pixels
+ *   lit [npts]          flat index y * p + x of the lit pixels, ascending: np.where(spup) order (:150)
+ *   nactu, ld_actu      commands per vector (stack-array actuators, then tip and tilt) and the row stride of `com`
+ *   if_data / if_indices / if_indptr   the file's CSR of the stack-array influence functions, [nactu - 2][npts]
+ *                       (drax.get_IF); turned into a per-pixel tap list, at most 16 taps per pixel
+ *   tt [npts][2]        the tip and tilt planes on the lit pixels
+ *   denmask, mask, otftel [N][N]   den . mask . (2 pi / lambda)^2, mask, otftel / max: made in float64 by the caller
+ *                       (:128-133; the mask is a threshold that fp32 transforms cannot reproduce at N = 2048) */
+typedef struct {
+  int32_t p, N, npts, nactu, ld_actu;
+  const int32_t *lit;
+  const float *if_data;
+  const int32_t *if_indices, *if_indptr;
+  const float *tt;
+  const float *denmask, *mask, *otftel;
+} aomarl_psfrec_desc;
+typedef struct aomarl_psfrec aomarl_psfrec;
+/* Allocates the whole workspace and transforms the pupil; nothing is allocated afterwards. */
+int aomarl_psfrec_create(const aomarl_psfrec_desc *desc, aomarl_psfrec **out);
+int aomarl_psfrec_destroy(aomarl_psfrec *r);
+/* com: DEVICE [nk][ld_actu], the command vectors Btt V_k (:154); w: DEVICE [nk], their weights e_k (any sign).
+ * For k = 0 .. nk-1 in order: m_k on the lit pixels, var += w_k m_k^2, acc += w_k |fft2 m_k|^2 (:155-159).  Every
+ * element of var and acc is summed in k order by the thread that owns it, without atomics: one call of nk vectors and
+ * several calls over the same vectors in the same order leave the same bits.  Asynchronous on `stream`. */
+int aomarl_psfrec_accumulate(aomarl_psfrec *r, const float *com, const float *w, int nk, void *stream);
+/* dphi, otf2, psf: DEVICE [N][N], any may be NULL (:163-168).  otf_other: DEVICE [N][N], the factor of the last
+ * product -- the fitting OTF Re fft2(psfortho) / max (:85-90) -- or NULL for otftel / max (:92).  The accumulated
+ * state is left as it is: a second call gives the same bits, and more vectors may be accumulated afterwards. */
+int aomarl_psfrec_finish(aomarl_psfrec *r, const float *otf_other, float *dphi, float *otf2, float *psf, void *stream);
+/* var = acc = 0 (synchronises the device) */
+int aomarl_psfrec_reset(aomarl_psfrec *r);
 /* PSF window + phase variance of st->tar_phase as it stands (pending, like aomarl_target_psf) */
 int aomarl_target_psf_buffer(aomarl_ctx *ctx, aomarl_state *st, int env_begin, int env_count,
                              void *stream);

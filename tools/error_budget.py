@@ -7,7 +7,10 @@ Without --checkpoints the integrator alone is analysed (6 x 6 tables); with it t
 sorted order = agent order, any of the three actor layouts BatchedSAC.load_model accepts) and zeta joins the table.
 Prints the reference's progress line every 100 frames and, at the end, the mean over environments of the per-
 contributor variance (the diagonal of cov, microns^2), the correlation table, the fitting term, the long-exposure
-Strehl and how far exp(-(variance of the sum + fitting)) closes on it."""
+Strehl and how far exp(-(variance of the sum + fitting)) closes on it.
+
+With --psf-rec the PSF of environment 0 is reconstructed from the covariance of its error buffers (ao_marl_amd.psf_rec,
+the reference's gamora.psf_rec_Vii) and its Strehl printed beside the loop's; --psf-rec-out FILE keeps otf2 and psf."""
 import argparse
 import os
 import sys
@@ -32,13 +35,17 @@ def main(argv=None):
                     help="first frame of the moments (0: the reference's cov_cor, preloop included)")
     ap.add_argument("--seed", type=int, default=200)
     ap.add_argument("--save", default=None, help=".npz of the histories of environment 0")
+    ap.add_argument("--psf-rec", action="store_true", help="reconstruct the long-exposure PSF of environment 0 (Vii)")
+    ap.add_argument("--psf-rec-out", default=None, help=".npz for otftel, otf2 and psf of --psf-rec")
     a = ap.parse_args(argv)
     from ao_marl_amd import roket
     from ao_marl_amd.env import VecAoEnv
     rl = dict(n_reverse_filtered_from_cmat=a.nfiltered)
     if a.modes is not None:
         rl["n_zernike_start_end"] = list(a.modes)
-    env = VecAoEnv(a.params, a.nenv, rl, n_agents_modal=a.agents, geo=True, frame_pipeline=False)
+    # an agent layout needs the range of modes it is dealt over (--modes); the integrator alone needs no layout
+    with_layout = a.modes is not None or a.checkpoints is not None
+    env = VecAoEnv(a.params, a.nenv, rl, n_agents_modal=a.agents if with_layout else None, geo=True, frame_pipeline=False)
     env.set_sim_seed(a.seed)                         # error_budget_multiple_agents.py:291-292
     policy = None
     if a.checkpoints:
@@ -51,7 +58,7 @@ def main(argv=None):
             sac.load_model(i, os.path.join(a.checkpoints, f))
         policy = sac.policy
     rk = roket.VecRoket(env, a.frames, a.preloop, policy=policy, gamma=a.gamma, accumulate_from=a.accumulate_from,
-                        keep_envs=(0,) if a.save else ())
+                        keep_envs=(0,) if a.save or a.psf_rec else (), psf_ortho_envs=(0,) if a.psf_rec else ())
     res = rk.run()
     names = res["contributors"]
     cov, cor = res["cov"].mean(axis=0), res["cor"].mean(axis=0)
@@ -79,6 +86,17 @@ def main(argv=None):
     if a.save:
         rk.save(a.save)
         print("histories of environment 0 -> %s" % a.save)
+    if a.psf_rec:
+        # a comparison, not a check: how closely a covariance of a few hundred frames explains the PSF is physics
+        from ao_marl_amd import psf_rec
+        with_zeta = policy is not None
+        otftel, otf2, psf = psf_rec.psf_rec_vii(rk, 0, fitting=True, rl=with_zeta)
+        bare = psf_rec.psf_rec_vii(rk, 0, fitting=False, rl=with_zeta)[2]
+        print("PSF reconstruction (Vii), environment 0: Strehl %.4f with the fitting OTF, %.4f without   |   loop: SR long "
+              "exposure %.4f, SR2 %.4f" % (float(psf.max()), float(bare.max()), float(res["SR"][0]), float(res["SR2"][0])))
+        if a.psf_rec_out:
+            np.savez(a.psf_rec_out, otftel=otftel, otf2=otf2, psf=psf, psf_without_fitting=bare)
+            print("otftel, otf2, psf -> %s" % a.psf_rec_out)
     return res
 
 
