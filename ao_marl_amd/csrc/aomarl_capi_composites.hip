@@ -217,7 +217,7 @@ int aomarl_next_part_two(aomarl_ctx *c, aomarl_state *st, int b, int n, const fl
 int aomarl_gemm_nt(int M, int N, int K, float alpha, const float *A, int lda, const float *B, int ldb,
                    float beta, float *C, int ldc, void *stream) {
   if (!A || !B || !C) return fail("gemm_nt: null pointer");
-  if (M < 0 || N < 0 || K < 0 || lda < K || ldb < K || ldc < N) return fail("gemm_nt: bad sizes");
+  if (M < 0 || N < 0 || K < 1 || lda < K || ldb < K || ldc < N) return fail("gemm_nt: bad sizes (K must be at least 1)");
   launch_gemm_nt(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, (hipStream_t)stream);
   LAUNCHCHK();
   return 0;
@@ -227,7 +227,7 @@ int aomarl_gemm_nt_split(int M, int N, int K, float alpha, const float *A, int l
                          float beta, float *C, int ldc, float scale_a, float scale_b, float *work,
                          long long work_floats, void *stream) {
   if (!A || !B || !C) return fail("gemm_nt_split: null pointer");
-  if (M < 0 || N < 0 || K < 0 || lda < K || ldb < K || ldc < N) return fail("gemm_nt_split: bad sizes");
+  if (M < 0 || N < 0 || K < 1 || lda < K || ldb < K || ldc < N) return fail("gemm_nt_split: bad sizes (K must be at least 1)");
   if ((lda & 3) || (ldb & 3) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15))
     return fail("gemm_nt_split: operands must be 16-byte aligned with leading dimensions that are multiples of 4");
   auto pow2 = [](float v) { int e; return v > 0.f && frexpf(v, &e) == 0.5f; };
@@ -238,6 +238,52 @@ int aomarl_gemm_nt_split(int M, int N, int K, float alpha, const float *A, int l
                  nullptr, nullptr, true, scale_a, scale_b);
   g_gemm_split_f16 = keep;
   LAUNCHCHK();
+  return 0;
+}
+
+// launch_gemm_nt as the loop calls it (workspace, split K, the slabs-only mode, pick_M), with the kernel, tile, k split
+// and block numbering forced through arguments -- no option is touched -- and a report of what ran.  For tests.
+int aomarl_gemm_nt_probe(int M, int N, int K, float alpha, const float *A, int lda, const float *B, int ldb,
+                         float beta, float *C, int ldc, float *work, long long work_floats, aomarl_gemm_probe *probe,
+                         void *stream) {
+  if (!A || !B || !C || !probe) return fail("gemm_nt_probe: null pointer");
+  if (M < 1 || N < 1 || K < 1 || lda < K || ldb < K || ldc < N) return fail("gemm_nt_probe: bad sizes");
+  if (work_floats < 0 || (work_floats > 0 && !work)) return fail("gemm_nt_probe: work_floats without work");
+  if (probe->kernel < 0 || probe->kernel > 3) return fail("gemm_nt_probe: kernel must be 0 (the library's choice), 1 (k_gemm_p), 2 (k_gemm_nt) or 3 (k_gemm_nt_h)");
+  if (probe->xcd < 0 || probe->xcd > 2) return fail("gemm_nt_probe: xcd must be 0 (the option), 1 (on) or 2 (off)");
+  if (probe->pick_M < 0 || (probe->pick_M > 0 && probe->pick_M > M)) return fail("gemm_nt_probe: pick_M must lie in 0 .. M");
+  float sa = 1.f, sb = 1.f;
+  if (probe->kernel == 3) {
+    auto pow2 = [](float v) { int e; return v > 0.f && frexpf(v, &e) == 0.5f; };
+    sa = probe->scale_a == 0.f ? 1.f : probe->scale_a;
+    sb = probe->scale_b == 0.f ? 1.f : probe->scale_b;
+    if (!pow2(sa) || !pow2(sb)) return fail("gemm_nt_probe: scale_a / scale_b must be powers of two");
+  }
+  if (probe->slabs_only && !(work && work_floats > 0)) return fail("gemm_nt_probe: slabs_only needs a workspace");
+  if (probe->epi_mode < 0 || probe->epi_mode > 2) return fail("gemm_nt_probe: epi_mode must be 0, 1 or 2");
+  if (probe->epi_mode && probe->slabs_only) return fail("gemm_nt_probe: epi_mode with slabs_only (no reduce runs)");
+  if (probe->epi_mode == 1 && (!probe->epi_com || probe->epi_ldcom < N)) return fail("gemm_nt_probe: epi_mode 1 needs epi_com with epi_ldcom >= N");
+  if (probe->epi_mode == 2 && (!probe->epi_action || !probe->epi_amode_inv || !probe->epi_freedom || probe->epi_nact < 1))
+    return fail("gemm_nt_probe: epi_mode 2 needs epi_action, epi_nact, epi_amode_inv and epi_freedom");
+  GemmEpi ep;
+  memset(&ep, 0, sizeof(ep));
+  ep.mode = probe->epi_mode; ep.com = probe->epi_com; ep.ldcom = probe->epi_ldcom; ep.gain = probe->epi_gain;
+  ep.gain_row = probe->epi_gain_row; ep.action = probe->epi_action; ep.nact = probe->epi_nact;
+  ep.amode_inv = probe->epi_amode_inv; ep.freedom = probe->epi_freedom;
+  GemmForce f;
+  memset(&f, 0, sizeof(f));
+  f.kernel = probe->kernel; f.wm = probe->wm; f.wn = probe->wn; f.ksplit = probe->ksplit; f.xcd = probe->xcd;
+  int nsplit = 0;
+  float alpha_out = alpha;
+  float *ws = work_floats > 0 ? work : nullptr;
+  const bool fused = launch_gemm_nt(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, (hipStream_t)stream, ws, (size_t)work_floats,
+                                    probe->epi_mode ? &ep : nullptr, probe->slabs_only ? &nsplit : nullptr, false, sa, sb,
+                                    &alpha_out, 128, probe->pick_M, &f);
+  if (f.error) return fail("gemm_nt_probe: refused %s", f.error);
+  LAUNCHCHK();
+  probe->r_kernel = f.r_kernel; probe->r_wm = f.r_wm; probe->r_wn = f.r_wn; probe->r_nz = f.r_nz; probe->r_kchunk = f.r_kchunk;
+  probe->r_slabs = nsplit; probe->r_alpha = alpha_out; probe->r_fused = fused ? 1 : 0;
+  probe->p_wm = f.pick.wm; probe->p_wn = f.pick.wn; probe->p_nz = f.pick.nz; probe->p_kchunk = f.pick.kchunk;
   return 0;
 }
 

@@ -25,6 +25,7 @@
 // dimensions that are multiples of 4 (the caller falls back to k_gemm_nt otherwise).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "aomarl_gemm_p_host.h"   // GemmPCfg, the tile menu, gemm_p_chunks / gemm_p_cost / gemm_p_pick, GP_KT
 
 #ifndef GP_TYPES
 #define GP_TYPES
@@ -37,7 +38,6 @@ struct __attribute__((packed, aligned(4))) gp_f4u { float v[4]; };
 // touch 16 different bank groups (a padded pitch of 36 made the staging writes of rows r, r + 1 collide: 34 % of the
 // LDS cycles were conflicts, profiles/r04_pmc_gemm_p.txt)
 #define GP_LD 32          // LDS row pitch (floats)
-#define GP_KT 32          // k-tile
 
 template <int WM, int WN>
 __global__ __launch_bounds__(256, 2) void k_gemm_p(int M, int N, int K, float alpha,
@@ -192,17 +192,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_p(int M, int N, int K, float al
   }
 }
 
-// ---- host side: configuration menu and launch -------------------------------------------------------------
-struct GemmPCfg {
-  int wm, wn;            // wave tile in 16-granules; block tile = (32 wm) x (32 wn)
-  int nz, kchunk;        // k-chunks and their length (a multiple of GP_KT)
-  int tiles_m, tiles_n;
-};
-
+// ---- host side: launch (configuration menu, cost model and pick: aomarl_gemm_p_host.h) --------------------
 static inline size_t gemm_p_lds_bytes(int wm, int wn) { return (size_t)2 * 32 * (wm + wn) * GP_LD * sizeof(float); }  // two buffers per operand
-
-// the instantiations the library carries
-#define GP_FOR_EACH_TILE(X) X(4, 4) X(4, 3) X(4, 2) X(2, 4) X(2, 3) X(2, 2) X(3, 3) X(3, 2)
 
 typedef void (*gemm_p_kernel_t)(int, int, int, float, const float *, int, const float *, int, float, float *, int, int, int,
                                 float *, int, int, int);
@@ -225,50 +216,6 @@ static inline bool gemm_p_prepare(int wm, int wn) {
     return false;
   done[wm][wn] = true;
   return true;
-}
-
-// kchunk for a split into (about) ns chunks: whole k-tiles, every chunk non-empty
-static inline void gemm_p_chunks(int K, int ns, int *kchunk, int *nz) {
-  const int kt = (K + GP_KT - 1) / GP_KT;
-  const int per = (kt + ns - 1) / ns;
-  *kchunk = per * GP_KT;
-  *nz = (kt + per - 1) / per;
-}
-
-// Cost model (cycles of the busiest SIMD, roughly): workgroups go round-robin over ncu CUs, two of them share a
-// CU's four SIMDs.  Per workgroup: k-tiles x (8 wm wn matrix instructions x 32 cycles + a barrier's skew) + fill
-// + the tile's stores; plus what the consumer pays for reading nz slabs.
-static inline double gemm_p_cost(int M, int N, int K, int wm, int wn, int ns, GemmPCfg *out) {
-  const int ncu = 256;
-  const int BM = 32 * wm, BN = 32 * wn;
-  GemmPCfg c;
-  c.wm = wm; c.wn = wn;
-  c.tiles_m = (M + BM - 1) / BM; c.tiles_n = (N + BN - 1) / BN;
-  gemm_p_chunks(K, ns, &c.kchunk, &c.nz);
-  const long long G = (long long)c.tiles_m * c.tiles_n * c.nz;
-  const long long per_cu = (G + ncu - 1) / ncu;
-  const double ktile = 8.0 * wm * wn * 32.0 + 250.0;
-  const double wg = (c.kchunk / GP_KT) * ktile + 2500.0 + 16.0 * wm * wn * 4.0;
-  // slabs: written once, read once by the consumer (~4 B/clk/CU effective each way)
-  const double slabs = c.nz > 1 ? 2.0 * c.nz * (double)M * N * 4.0 / (ncu * 8.0) : 0.0;
-  if (out) *out = c;
-  return per_cu * wg + slabs;
-}
-
-static inline GemmPCfg gemm_p_pick(int M, int N, int K, size_t ws_floats, int max_split) {
-  GemmPCfg best = {0, 0, 0, 0, 0, 0};
-  double bc = -1.0;
-#define GP_TRY(a, b)                                                                      \
-  for (int ns = 1; ns <= max_split; ns++) {                                               \
-    GemmPCfg c;                                                                           \
-    const double cost = gemm_p_cost(M, N, K, a, b, ns, &c);                               \
-    if (c.nz > 1 && (size_t)c.nz * M * N > ws_floats) break;                              \
-    if (c.nz < ns) continue;                                                              \
-    if (bc < 0 || cost < bc) { bc = cost; best = c; }                                     \
-  }
-  GP_FOR_EACH_TILE(GP_TRY)
-#undef GP_TRY
-  return best;
 }
 
 // launch with a given configuration (P may be null when cfg.nz == 1)

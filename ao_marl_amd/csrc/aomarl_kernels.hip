@@ -554,23 +554,46 @@ static unsigned *gemm_sat_counter() {
 //      the caller's next kernel sums the partial tiles ws[z][M][N] itself (*nsplit_out = count,
 //      0 = C is final).
 // fast: the split-f16 kernel may be used (internal call sites whose operands are inside its range)
+// force (aomarl_gemm_nt_probe, tests only; null everywhere else): the kernel, tile, k split and block numbering to
+//      take instead of the library's own, and a report of what was launched.  A forced value that cannot be had
+//      is refused (force->error names the argument, nothing is launched), never replaced.
+struct GemmForce {
+  int kernel;            // 0 = the library's choice, 1 = k_gemm_p, 2 = k_gemm_nt (also on aligned operands), 3 = k_gemm_nt_h
+  int wm, wn;            // k_gemm_p's tile (both or neither)
+  int ksplit;            // k-chunks asked for
+  int xcd;               // 0 = the "gemm_xcd_map" option, 1 = on, 2 = off
+  const char *error;     // out: null, or what was refused
+  int r_kernel, r_wm, r_wn, r_nz, r_kchunk;       // out: what was launched
+  GemmPCfg pick;         // out: gemm_p_pick for this shape and workspace, computed afresh beside the memo (wm == 0: k_gemm_p not considered)
+};
 bool launch_gemm_nt(int M, int N, int K, float alpha, const float *A, int lda, const float *B,
                     int ldb, float beta, float *C, int ldc, hipStream_t s, float *ws = nullptr,
                     size_t ws_floats = 0, const GemmEpi *epi = nullptr, int *nsplit_out = nullptr,
                     bool fast = false, float sa = 1.f, float sb = 1.f, float *alpha_out = nullptr,
-                    int min_chunk = 128, int pick_M = 0) {
+                    int min_chunk = 128, int pick_M = 0, GemmForce *force = nullptr) {
   // alpha_out: the factor the caller must apply to the partial tiles when it sums them itself
   // pick_M > 0: tile and split-K as a product of pick_M rows would get them (a sum's order depends on the k split
   //             alone: M rows at once then give, bit for bit, what M / pick_M products of pick_M rows give)
   if (nsplit_out) *nsplit_out = 0;
   if (alpha_out) *alpha_out = alpha;
-  if (M <= 0 || N <= 0) return false;
+  if (M <= 0 || N <= 0 || K <= 0) return false;  // (an empty sum: the entry points refuse K == 0, no internal product has one)
   const int Mp = pick_M > 0 ? pick_M : M;
   const size_t wsp = pick_M > 0 ? (size_t)((double)ws_floats * Mp / M) : ws_floats;     // the part's share of the workspace
   const int bx = (N + 63) / 64, by = (M + 63) / 64, byp = (Mp + 63) / 64;
   int nsplit = 1;
   bool al = (lda % 4 == 0) && (ldb % 4 == 0) && (((uintptr_t)A & 15) == 0) &&
             (((uintptr_t)B & 15) == 0);
+  if (force) {
+    force->error = nullptr;
+    force->r_kernel = force->r_wm = force->r_wn = force->r_nz = force->r_kchunk = 0;
+    force->pick = GemmPCfg{0, 0, 0, 0, 0, 0};
+    if ((force->kernel == 1 || force->kernel == 3 || force->wm || force->wn) && !al) { force->error = "kernel / wm / wn (operands not 16-byte aligned)"; return false; }
+    if ((force->wm || force->wn) && !gemm_p_on_menu(force->wm, force->wn)) { force->error = "wm / wn (not an instantiated tile)"; return false; }
+    if ((force->wm || force->wn) && force->kernel != 0 && force->kernel != 1) { force->error = "wm / wn (k_gemm_p only)"; return false; }
+    if (force->ksplit < 0 || (force->ksplit > 1 && !ws)) { force->error = "ksplit (no workspace)"; return false; }
+    if (force->kernel == 2) al = false;          // the element-wise kernel on aligned operands
+  }
+  const int xcd = force && force->xcd ? (force->xcd == 1 ? 1 : 0) : g_gemm_xcd;
   if (ws && bx * byp < 384) {
     // Split K so that the launch is as short as its slowest CU: blocks go round-robin over the 256 CUs, a CU
     // that gets one block more than the others sets the duration (528 blocks = 2.06 per CU took as long as 768
@@ -596,7 +619,7 @@ bool launch_gemm_nt(int M, int N, int K, float alpha, const float *A, int lda, c
       }
     }
   }
-  const bool split_f16 = al && fast && g_gemm_split_f16;
+  const bool split_f16 = al && ((fast && g_gemm_split_f16) || (force && force->kernel == 3));
   if (al && !split_f16) {
     // round 4: the balanced kernel; tile and k split from its own cost model (memoised per shape)
     struct Memo { int M, N, K; size_t ws; GemmPCfg c; };
@@ -604,7 +627,12 @@ bool launch_gemm_nt(int M, int N, int K, float alpha, const float *A, int lda, c
     static thread_local int memo_n = 0;
     const size_t wsf = ws ? wsp : 0;
     const GemmPCfg *cfg = nullptr;
-    for (int i = 0; i < memo_n; i++)
+    GemmPCfg fresh;
+    if (force) {                                 // a probe call reports the pick computed afresh
+      force->pick = fresh = gemm_p_pick(Mp, N, K, wsf, ws ? 16 : 1);
+      if (force->wm || force->ksplit) cfg = &fresh;          // forced: the memo is neither read nor written
+    }
+    for (int i = 0; i < memo_n && !cfg; i++)
       if (memo[i].M == Mp && memo[i].N == N && memo[i].K == K && memo[i].ws == wsf) { cfg = &memo[i].c; break; }
     if (!cfg) {
       Memo &m = memo[memo_n < 16 ? memo_n++ : (memo_n = 1, 0)];
@@ -613,11 +641,17 @@ bool launch_gemm_nt(int M, int N, int K, float alpha, const float *A, int lda, c
       cfg = &m.c;
     }
     GemmPCfg mine = *cfg;                        // (pick_M: the part's tile and k split over this product's rows)
+    if (force && (force->wm || force->ksplit)) {   // forced tile and / or k split: the other one stays the pick's
+      gemm_p_cost(Mp, N, K, force->wm ? force->wm : mine.wm, force->wm ? force->wn : mine.wn,
+                  force->ksplit ? force->ksplit : mine.nz, &mine);
+      if (mine.nz > 1 && (size_t)mine.nz * M * N > ws_floats) { force->error = "ksplit (the slabs do not fit work_floats)"; return false; }
+    }
     if (mine.wm > 0) mine.tiles_m = (M + 32 * mine.wm - 1) / (32 * mine.wm);
     cfg = &mine;
-    if (cfg->wm > 0 && gemm_p_launch(*cfg, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, ws, g_gemm_xcd, s)) {
+    if (cfg->wm > 0 && gemm_p_launch(*cfg, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, ws, xcd, s)) {
       g_arith[AR_GEMM_F32]++;
       nsplit = cfg->nz;
+      if (force) { force->r_kernel = 1; force->r_wm = cfg->wm; force->r_wn = cfg->wn; force->r_nz = cfg->nz; force->r_kchunk = cfg->kchunk; }
       if (nsplit > 1) {
         const long long tot = (long long)M * N;
         if (nsplit_out) { *nsplit_out = nsplit; return false; }
@@ -631,18 +665,23 @@ bool launch_gemm_nt(int M, int N, int K, float alpha, const float *A, int lda, c
       }
       return false;
     }
+    if (force && (force->kernel == 1 || force->wm)) { force->error = "kernel (k_gemm_p could not be launched)"; return false; }
   }
+  if (force && force->ksplit) nsplit = force->ksplit;
   int kchunk = ((K + nsplit - 1) / nsplit + 31) & ~31;
   if (al)                                        // whole groups of three k-tiles (g3_mainloop / gh_mainloop)
     kchunk = ((K + nsplit - 1) / nsplit + 95) / 96 * 96;
   nsplit = (K + kchunk - 1) / kchunk;
+  if (force && force->ksplit && nsplit > 1 && (size_t)nsplit * M * N > ws_floats) { force->error = "ksplit (the slabs do not fit work_floats)"; return false; }
   dim3 grid(bx, by, nsplit);
-  unsigned *sat = (al && fast && g_gemm_split_f16) ? gemm_sat_counter() : nullptr;
-  if (al && fast && g_gemm_split_f16 && sat) {
+  unsigned *sat = split_f16 ? gemm_sat_counter() : nullptr;
+  if (force && force->kernel == 3 && !sat) { force->error = "kernel (no saturation counter for k_gemm_nt_h)"; return false; }
+  if (force) { force->r_kernel = split_f16 && sat ? 3 : 2; force->r_wm = force->r_wn = 2; force->r_nz = nsplit; force->r_kchunk = kchunk; }
+  if (split_f16 && sat) {
     alpha /= (sa * sb);                            // also what the split-K reduce below applies
     if (alpha_out) *alpha_out = alpha;
     hipLaunchKernelGGL(k_gemm_nt_h, grid, dim3(256), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C,
-                       ldc, kchunk, ws, sa, sb, g_gemm_xcd, sat);
+                       ldc, kchunk, ws, sa, sb, xcd, sat);
     g_arith[AR_GEMM_SPLIT]++;
   }
   else {

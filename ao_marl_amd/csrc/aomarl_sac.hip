@@ -643,3 +643,28 @@ int gemm_g_batched(int batch, bool ak, bool bk, int M, int N, int K, const float
   if (gemm_g_launch(batch, ak, bk, g, 0, 0, s)) return fail("gemm_batched: k_gemm_g launch failed");
   return 0;
 }
+
+// k_gemm_g with everything its launch takes (mask and column-sum epilogues, forced tiles), for tests
+int aomarl_gemm_g_probe(const aomarl_gemm_g_args *p, void *stream) {
+  if (!p) return fail("gemm_g_probe: null pointer");
+  if (!p->A || !p->B || !p->C) return fail("gemm_g_probe: null operand");
+  if (p->groups < 1 || p->M < 1 || p->N < 1 || p->K < 1) return fail("gemm_g_probe: bad sizes");
+  const bool ak = p->ak != 0, bk = p->bk != 0;
+  if (((uintptr_t)p->A & 15) || ((uintptr_t)p->B & 15)) return fail("gemm_g_probe: A and B must be 16-byte aligned");
+  if ((p->lda & 3) || (p->ldb & 3)) return fail("gemm_g_probe: lda and ldb must be multiples of 4");
+  if ((p->sA & 3) || (p->sB & 3)) return fail("gemm_g_probe: sA and sB must be multiples of 4");
+  if (p->lda < (ak ? p->K : p->M) || p->ldb < (bk ? p->K : p->N)) return fail("gemm_g_probe: lda / ldb shorter than a row");
+  if (p->ldc < p->N || (p->mask && p->ldm < p->N)) return fail("gemm_g_probe: ldc / ldm shorter than a row");
+  if (p->colsum && bk) return fail("gemm_g_probe: colsum needs an n-contiguous B (bk == 0)");
+  const bool tile_ok = (p->force_wm == 0 || p->force_wm == 2 || p->force_wm == 4) &&
+                       (p->force_wn == 0 || p->force_wn == 2 || p->force_wn == 4);
+  if (!tile_ok) return fail("gemm_g_probe: force_wm / force_wn must be 0, 2 or 4");
+  GemmGArgs g;
+  memset(&g, 0, sizeof(g));
+  g.M = p->M; g.N = p->N; g.K = p->K;
+  g.A = p->A; g.lda = p->lda; g.sA = p->sA; g.B = p->B; g.ldb = p->ldb; g.sB = p->sB; g.C = p->C; g.ldc = p->ldc; g.sC = p->sC;
+  g.bias = p->bias; g.sBias = p->sBias; g.relu = p->relu;
+  g.mask = p->mask; g.ldm = p->ldm; g.sM = p->sM; g.colsum = p->colsum; g.sCs = p->sCs;
+  if (gemm_g_launch(p->groups, ak, bk, g, p->force_wm, p->force_wn, (hipStream_t)stream)) return fail("gemm_g_probe: k_gemm_g launch failed");
+  return 0;
+}

@@ -193,9 +193,41 @@ SYMBOLS = [
     ("aomarl_gemm_nt_split", _i, [_i, _i, _i, _f, _vp, _i, _vp, _i, _f, _vp, _i, _f, _f, _vp, C.c_longlong, _vp]),
     ("aomarl_gemm_nt_batched", _i, [_i, _i, _i, _i, _vp, _i, C.c_longlong, _vp, _i, C.c_longlong,
                                     _vp, C.c_longlong, _vp, _i, C.c_longlong, _i, _vp]),
+    # the two probes of the GEMM conformance tests (tests/test_gpu_gemm_exact.py): every kernel, tile and k split forced
+    # through arguments; the struct pointers are GemmProbe / GemmGArgs below, passed with ctypes.byref
+    ("aomarl_gemm_nt_probe", _i, [_i, _i, _i, _f, _vp, _i, _vp, _i, _f, _vp, _i, _vp, C.c_longlong, _vp, _vp]),
+    ("aomarl_gemm_g_probe", _i, [_vp, _vp]),
 ]
 
 _lib = None
+
+
+GEMM_KERNEL_P, GEMM_KERNEL_NT, GEMM_KERNEL_NT_H = 1, 2, 3
+GEMM_XCD_ON, GEMM_XCD_OFF = 1, 2
+
+
+class GemmProbe(C.Structure):
+    """aomarl_gemm_probe (include/aomarl.h): forcing fields (0 = the library's choice), then the report"""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "wm", "wn", "ksplit", "xcd", "pick_M", "slabs_only")] + \
+               [("scale_a", C.c_float), ("scale_b", C.c_float)] + \
+               [(n, C.c_int32) for n in ("r_kernel", "r_wm", "r_wn", "r_nz", "r_kchunk", "r_slabs")] + \
+               [("r_alpha", C.c_float)] + \
+               [(n, C.c_int32) for n in ("p_wm", "p_wn", "p_nz", "p_kchunk")] + \
+               [(n, C.c_int32) for n in ("epi_mode", "epi_ldcom", "epi_nact")] + [("epi_gain", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("epi_com", "epi_gain_row", "epi_action", "epi_amode_inv", "epi_freedom")] + \
+               [("r_fused", C.c_int32)]
+
+
+class GemmGArgs(C.Structure):
+    """aomarl_gemm_g_args (include/aomarl.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("groups", "ak", "bk", "M", "N", "K")] + \
+               [("A", C.c_void_p), ("lda", C.c_int32), ("sA", C.c_longlong),
+                ("B", C.c_void_p), ("ldb", C.c_int32), ("sB", C.c_longlong),
+                ("C", C.c_void_p), ("ldc", C.c_int32), ("sC", C.c_longlong),
+                ("bias", C.c_void_p), ("sBias", C.c_longlong), ("relu", C.c_int32),
+                ("mask", C.c_void_p), ("ldm", C.c_int32), ("sM", C.c_longlong),
+                ("colsum", C.c_void_p), ("sCs", C.c_longlong),
+                ("force_wm", C.c_int32), ("force_wn", C.c_int32)]
 
 
 class SacDesc(C.Structure):

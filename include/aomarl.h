@@ -778,7 +778,8 @@ int aomarl_next_part_two(aomarl_ctx *ctx, aomarl_state *st, int env_begin, int e
                          const float *action_dev, void *stream);
 
 /* generic fp32 MFMA GEMM used by the calls above, exported for tests:
- * C[M][N] = alpha * A[M][K] . B[N][K]^T + beta * C ; device pointers, row-major, ld in floats */
+ * C[M][N] = alpha * A[M][K] . B[N][K]^T + beta * C ; device pointers, row-major, ld in floats; K >= 1 (an empty
+ * sum is refused, here and in aomarl_gemm_nt_split) */
 int aomarl_gemm_nt(int M, int N, int K, float alpha, const float *A, int lda, const float *B,
                    int ldb, float beta, float *C, int ldc, void *stream);
 
@@ -790,6 +791,72 @@ int aomarl_gemm_nt(int M, int N, int K, float alpha, const float *A, int lda, co
 int aomarl_gemm_nt_split(int M, int N, int K, float alpha, const float *A, int lda, const float *B, int ldb,
                          float beta, float *C, int ldc, float scale_a, float scale_b, float *work,
                          long long work_floats, void *stream);
+
+/* aomarl_gemm_nt as the loop's products call it -- with a split-K workspace, so that k_gemm_p writes partial slabs
+ * work[z][M][N] and k_gemm_reduce sums them -- plus forcing and a report.  Exported for tests: the exact-arithmetic
+ * conformance tests (tests/test_gpu_gemm_exact.py) run every kernel, tile instantiation and k split through it.
+ * Forcing fields, 0 = the library's own choice (then the call goes through the per-shape memo like any other):
+ *   kernel      1 = k_gemm_p, 2 = k_gemm_nt (also on 16-byte aligned operands), 3 = k_gemm_nt_h (scale_a / scale_b:
+ *               powers of two as in aomarl_gemm_nt_split, 0 = 1)
+ *   wm, wn      k_gemm_p's block tile (32 wm) x (32 wn); must be one of the instantiated tiles
+ *   ksplit      k-chunks asked for (whole k-tiles per chunk: fewer may come out, see r_nz)
+ *   xcd         1 = blocks renumbered by k-chunk per XCD, 2 = plain order, 0 = the "gemm_xcd_map" option
+ *   pick_M      tile and k split as a product of pick_M rows would get them
+ *   slabs_only  no reduce is launched and C is left untouched when the product was split: the caller sums
+ *               r_slabs slabs work[z][M][N] and multiplies by r_alpha (r_slabs == 0: C is final)
+ * Report: r_kernel (1 / 2 / 3), r_wm, r_wn (2, 2 for the 64 x 64 kernels), r_nz chunks of r_kchunk, and p_*: what
+ * k_gemm_p's cost model picks for this shape and workspace, computed afresh (p_wm == 0: operands not aligned).
+ * epi_mode   1: C = v, epi_com[m][n] += (epi_gain_row ? epi_gain_row[m] : epi_gain) * v  (the integrator);
+ *            2: C = v + epi_action[m][j] * epi_freedom[n] where j = epi_amode_inv[n] >= 0  (the agents' action);
+ *            applied by the reduce only when the product was split: r_fused says whether it was (else C = v alone,
+ *            as for the library's own callers, who then run the step themselves).  Not with slabs_only.
+ * A forced tile outside the menu, a forced kernel the operands' alignment rules out, or a forced split whose slabs
+ * do not fit work_floats is an error that names the argument; nothing is launched and nothing is substituted.
+ * No option is read for a forced field and none is set.  The per-shape memo of tile and k split is the library's own
+ * path: it is read and written whenever both are left to the library (also when only kernel, xcd or pick_M is
+ * forced), and neither read nor written when wm / wn or ksplit is forced. */
+typedef struct aomarl_gemm_probe {
+  int32_t kernel, wm, wn, ksplit, xcd, pick_M, slabs_only;
+  float scale_a, scale_b;
+  int32_t r_kernel, r_wm, r_wn, r_nz, r_kchunk, r_slabs;
+  float r_alpha;
+  int32_t p_wm, p_wn, p_nz, p_kchunk;
+  /* the consumer's step folded into the split-K reduce (k_gemm_reduce_epi), epi_mode 0 = none: */
+  int32_t epi_mode, epi_ldcom, epi_nact;
+  float epi_gain;
+  float *epi_com;
+  const float *epi_gain_row, *epi_action;
+  const int32_t *epi_amode_inv;
+  const float *epi_freedom;
+  int32_t r_fused;
+} aomarl_gemm_probe;
+int aomarl_gemm_nt_probe(int M, int N, int K, float alpha, const float *A, int lda, const float *B, int ldb,
+                         float beta, float *C, int ldc, float *work, long long work_floats, aomarl_gemm_probe *probe,
+                         void *stream);
+
+/* The learner's grouped GEMM (k_gemm_g, csrc/aomarl_gemm_g.h) with everything its launch takes.  Exported for tests:
+ *   C[g][M][N] = epilogue( opA(A[g]) . opB(B[g]) ),  g < groups
+ *   ak: A is [M][K] (k contiguous), else [K][M];  bk: B is [N][K], else [K][N]
+ *   epilogue: + bias[g][n] (may be NULL), ReLU (relu != 0), zero where mask[g][m][n] <= 0 (mask may be NULL);
+ *   colsum (may be NULL; only with bk == 0): colsum[g][n] = sum_k B[g][k][n], written once
+ *   force_wm, force_wn: block tile (32 wm) x (32 wn) with wm, wn in {2, 4}; 0 = the library's pick
+ * Refused, as the kernel cannot take them: A or B not 16-byte aligned, lda / ldb / sA / sB not multiples of 4,
+ * a leading dimension shorter than its row, colsum with bk != 0, a tile that is not instantiated.
+ * Not restricted, because the kernel reads and writes them through 4-byte aligned accesses (16-byte pieces of C, bias
+ * and mask are packed float quadruples, the ragged end of a row goes element by element): C, bias, mask and colsum at
+ * any float address, any ldc / ldm >= N, any sC / sBias / sM / sCs (the tests run ldc = N + 3 and ldm = N + 1). */
+typedef struct aomarl_gemm_g_args {
+  int32_t groups, ak, bk, M, N, K;
+  const float *A; int32_t lda; long long sA;
+  const float *B; int32_t ldb; long long sB;
+  float *C; int32_t ldc; long long sC;
+  const float *bias; long long sBias;
+  int32_t relu;
+  const float *mask; int32_t ldm; long long sM;
+  float *colsum; long long sCs;
+  int32_t force_wm, force_wn;
+} aomarl_gemm_g_args;
+int aomarl_gemm_g_probe(const aomarl_gemm_g_args *args, void *stream);
 
 /* batched fp32 MFMA GEMM with fused bias + ReLU for the stacked SAC MLPs (one batch entry per
  * agent): C[b][M][N] = act(A[b][M][K] . B[b][N][K]^T + bias[b][N]); B is in nn.Linear layout
