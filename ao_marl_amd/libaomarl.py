@@ -13,7 +13,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 # AOMARL_LIB: another build of the same library (A/B measurements of kernel variants, csrc/Makefile `variant`)
 LIB_PATH = os.environ.get("AOMARL_LIB") or os.path.join(HERE, "libaomarl_hip.so")
-MAX_LAYERS, MAX_DMS, ABI_VERSION = 8, 4, 3
+MAX_LAYERS, MAX_DMS, ABI_VERSION = 8, 4, 4
 PRECISION_F32, PRECISION_SPLIT_F16 = 0, 1
 
 DM_PZT, DM_TT = 0, 1
@@ -174,6 +174,10 @@ SYMBOLS = [
     ("aomarl_psfrec_accumulate", _i, [_vp, _vp, _vp, _i, _vp]),
     ("aomarl_psfrec_finish", _i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     ("aomarl_psfrec_reset", _i, [_vp]),
+    ("aomarl_groot_create", _i, [_vp, C.POINTER(C.c_void_p)]),
+    ("aomarl_groot_destroy", _i, [_vp]),
+    ("aomarl_groot_form", _i, [_vp, _vp, _vp, _vp, _i, _vp, _i, C.c_longlong, _vp]),
+    ("aomarl_groot_sandwich", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp]),
     ("aomarl_target_psf_buffer", _i, _range + [_vp]),
     ("aomarl_set_geo", _i, [_vp, _fp]),
     ("aomarl_geo_workspace_floats", C.c_size_t, [_vp, _i]),
@@ -283,6 +287,25 @@ class PsfRecDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("p", "N", "npts", "nactu", "ld_actu")] + \
                [("lit", _ip), ("if_data", _fp), ("if_indices", _ip), ("if_indptr", _ip), ("tt", _fp),
                 ("denmask", _fp), ("mask", _fp), ("otftel", _fp)]
+
+
+_dp = C.POINTER(C.c_double)
+GROOT_CERR, GROOT_CALIAS_XX, GROOT_CALIAS_YY, GROOT_DCMM_XX, GROOT_DCMM_YY = range(5)
+
+
+class GrootDesc(C.Structure):
+    """aomarl_groot_desc (include/aomarl.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("n_max", "batch_max", "m_max", "k_max")] + [("tabx", _dp), ("taby", _dp)]
+
+
+class GrootFormDesc(C.Structure):
+    """aomarl_groot_form_desc (include/aomarl.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("model", "batch", "nlayers", "npts")] + [("x0", C.c_double)] + \
+               [(n, _dp) for n in ("w", "sx", "sy", "L0")]
+
+
+def dptr(a):
+    return a.ctypes.data_as(_dp)
 
 
 class AomarlError(RuntimeError):

@@ -166,6 +166,36 @@ def cmat_with_btt(D, Btt, nfilt):
     return (_btt_filtered(Btt, nfilt) @ projector_wfs2modes(D, Btt, nfilt)).astype(np.float32)
 
 
+def nact_geom(i1, j1, pitch, coupling, dim):
+    """The stack-array mirror's coupling matrix Nact [n][n], float32 (shesha/ao/tomo.py:217-259 create_nact_geom): column
+    a holds, over the kept actuators, what actuator a couples into its eight lattice neighbours -- `coupling` along the
+    axes, coupling^2 on the diagonals, 1 on itself.  i1, j1: the actuators' corner pixels on the dim x dim support
+    (dim = n2 - n1 + 1), pitch in pixels.  The reference reads its rows in the row-major order of the lit cells of a mask
+    and lets a neighbour left of or above the support wrap round (a negative index); one right of or below it is an
+    IndexError there and a ValueError here."""
+    i1, j1 = np.asarray(i1, dtype=np.int64), np.asarray(j1, dtype=np.int64)
+    n, p, dim = i1.size, int(pitch), int(dim)
+    if j1.size != n or p < 1:
+        raise ValueError("nact_geom: %d / %d corner pixels, pitch %r" % (n, j1.size, pitch))
+    cell = j1 * dim + i1
+    cells = np.unique(cell)
+    if cells.size != n or i1.min() < 0 or j1.min() < 0 or i1.max() >= dim or j1.max() >= dim:
+        raise ValueError("nact_geom: the actuators do not sit on %d different pixels of the %d x %d support" % (n, dim, dim))
+    Nact = np.zeros((n, n), dtype=np.float32)
+    c1, c2 = np.float32(coupling), np.float32(coupling ** 2)
+    stencil = [(0, 0, np.float32(1))] + [(dj, di, c1) for dj, di in ((0, -1), (-1, 0), (0, 1), (1, 0))] + \
+        [(dj, di, c2) for dj, di in ((-1, -1), (-1, 1), (1, 1), (1, -1))]
+    for dj, di, v in stencil:
+        jj, ii = j1 + dj * p, i1 + di * p
+        if jj.max() >= dim or ii.max() >= dim:
+            raise ValueError("nact_geom: a neighbour at pitch %d leaves the %d x %d support" % (p, dim, dim))
+        target = np.where(jj < 0, jj + dim, jj) * dim + np.where(ii < 0, ii + dim, ii)
+        row = np.searchsorted(cells, target)
+        hit = (row < n) & (cells[np.minimum(row, n - 1)] == target)
+        Nact[row[hit], np.arange(n)[hit]] = v
+    return Nact
+
+
 def geo_projector(IF):
     """Projection matrix of the geometric ("GEO") controller, COMPASS's sutra_controller_geo as the
     reference configures it (rtc_init.py:418-448: influence functions of the controller's DMs on

@@ -426,14 +426,47 @@ class VecRoket(object):
         idx = [self.keep_envs.index(e) for e in envs]
         return npz_dict(self.hist, idx, envs, self.n_preloop, self.results(), self.sup.cal, self.cmat_h,
                         None if self.psf_ortho is None else (self.psf_ortho / max(self._n_behind, 1)).cpu().numpy(),
-                        spup=self.sup.s.spupil, tar_lambda=self.sup.s.tar_lambda, psf_ortho_envs=self.psf_ortho_envs)
+                        spup=self.sup.s.spupil, tar_lambda=self.sup.s.tar_lambda, psf_ortho_envs=self.psf_ortho_envs,
+                        **self.groot_keys())
+
+    def groot_keys(self):
+        """What the GROOT model reads beside the matrices (groot.py): the stack array's coupling matrix and actuator
+        positions, and the parameters under the reference's attribute names, as they stand now (set_wind / set_r0)."""
+        from . import modal
+        sup = self.sup
+        ps, dm = sup.config, sup.s.dms[0]
+        if dm.type != "pzt":
+            raise NotImplementedError("VecRoket: the first mirror of the controller is %r, not a stack array" % (dm.type,))
+        a, w, cz = ps.p_atmos, ps.p_wfss[0], np.cos(np.deg2rad(float(ps.p_geom.zenithangle)))
+        frac = np.asarray(a.frac, dtype=np.float64)
+        one = lambda v: np.asarray([v], dtype=np.float64)                  # noqa: E731
+        params = {
+            "_Param_atmos__r0": float(a.r0), "_Param_atmos__alt": np.asarray(a.alt, dtype=np.float64) / cz,
+            "_Param_atmos__L0": np.asarray(a.L0, dtype=np.float64),
+            "_Param_atmos__windspeed": np.asarray(a.windspeed, dtype=np.float64),
+            "_Param_atmos__winddir": np.asarray(a.winddir, dtype=np.float64), "_Param_atmos__frac": frac / frac.sum(),
+            "_Param_atmos__nscreens": int(a.nscreens), "_Param_loop__ittime": float(ps.p_loop.ittime),
+            "_Param_controller__gain": float(sup.gain), "_Param_wfs__xpos": one(w.xpos), "_Param_wfs__ypos": one(w.ypos),
+            "_Param_wfs__Lambda": one(w.Lambda), "_Param_wfs__nxsub": np.asarray([w.nxsub]), "_Param_wfs__npix": np.asarray([w.npix]),
+            "_Param_wfs__noise": one(w.noise), "_Param_wfs__zerop": one(w.zerop), "_Param_wfs__gsmag": one(w.gsmag),
+            "_Param_wfs__optthroughput": one(w.optthroughput), "_Param_wfs__pixsize": one(sup.s.cog_scale),
+            "_Param_tel__diam": float(ps.p_tel.diam), "_Param_tel__cobs": float(ps.p_tel.cobs),
+            "_Param_geom__pupdiam": int(sup.sysm.geom.pupdiam), "_Param_dm__nact": np.asarray([d.nact for d in ps.p_dms]),
+            "_Param_dm__unitpervolt": np.asarray([d.unitpervolt for d in ps.p_dms], dtype=np.float64),
+            # the sensor's own valid sub-apertures, in the order of its slopes (p_wfs._validsubsx, in pixels of the image)
+            "_Param_wfs___validsubsx": np.asarray(sup.s.validsubsx), "_Param_wfs___validsubsy": np.asarray(sup.s.validsubsy)}
+        return dict(nact=modal.nact_geom(dm.i1, dm.j1, dm.pitch, ps.p_dms[sup.s.dm_index[0]].coupling, dm.n2 - dm.n1 + 1),
+                    dm_xpos=dm.xpos, dm_ypos=dm.ypos, params=params)
 
 
-def npz_dict(hist, idx, envs, n_preloop, res, cal, cmat, psf_ortho=None, spup=None, tar_lambda=None, psf_ortho_envs=None):
+def npz_dict(hist, idx, envs, n_preloop, res, cal, cmat, psf_ortho=None, spup=None, tar_lambda=None, psf_ortho_envs=None,
+             nact=None, dm_xpos=None, dm_ypos=None, params=None):
     """The dictionary save() writes.  hist: per-frame lists, "x" [7][kept][nactu] and "com", "slopes", "wf_com",
     "alias_meas", "trunc_meas" [kept][.]; idx: positions of `envs` among the kept environments.  spup (the reference's
     name, drax.get_pup) and tar_lambda (its attribute _Param_target__Lambda) are what the PSF reconstruction reads
-    beside the histories (psf_rec.py); psfortho_envs: the environments psfortho's leading axis runs over."""
+    beside the histories (psf_rec.py); psfortho_envs: the environments psfortho's leading axis runs over.  nact ("Nact",
+    tomo.create_nact_geom), dm_xpos / dm_ypos ("dm.xpos", "dm.ypos") and params (the reference's attributes, a mapping
+    "_Param_<class>__<name>" -> value) are what the GROOT model reads (groot.py)."""
     x = np.stack(hist["x"])[n_preloop:]                                # [frames][7][kept][nactu]
     h = lambda k: np.stack(hist[k])[n_preloop:][:, idx].transpose(1, 2, 0)       # noqa: E731
     xk = lambda k: x[:, k][:, idx].transpose(1, 2, 0)                  # noqa: E731
@@ -457,6 +490,16 @@ def npz_dict(hist, idx, envs, n_preloop, res, cal, cmat, psf_ortho=None, spup=No
         d["spup"] = np.asarray(spup, dtype=np.float32)
     if tar_lambda is not None:
         d["tar_lambda"] = np.asarray([tar_lambda], dtype=np.float64)
+    if nact is not None:
+        d["Nact"] = np.asarray(nact, dtype=np.float32)
+    if dm_xpos is not None:
+        d["dm.xpos"] = np.asarray(dm_xpos)
+    if dm_ypos is not None:
+        d["dm.ypos"] = np.asarray(dm_ypos)
+    for k, v in (params or {}).items():
+        if not k.startswith("_Param_"):
+            raise ValueError("npz_dict: params key %r is not one of the reference's attribute names (_Param_...)" % (k,))
+        d[k] = np.asarray(v)
     return d
 
 

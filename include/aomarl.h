@@ -26,7 +26,7 @@ extern "C" {
 
 #define AOMARL_MAX_LAYERS 8
 #define AOMARL_MAX_DMS 4
-#define AOMARL_ABI_VERSION 3
+#define AOMARL_ABI_VERSION 4
 
 enum { AOMARL_DM_PZT = 0, AOMARL_DM_TT = 1 };
 
@@ -712,6 +712,53 @@ int aomarl_psfrec_accumulate(aomarl_psfrec *r, const float *com, const float *w,
 int aomarl_psfrec_finish(aomarl_psfrec *r, const float *otf_other, float *dphi, float *otf2, float *psf, void *stream);
 /* var = acc = 0 (synchronises the device) */
 int aomarl_psfrec_reset(aomarl_psfrec *r);
+/* GROOT: the residual-error covariance MODELLED from the atmosphere's structure functions (guardians/groot.py; the
+ * structure functions: guardians/starlord.py:10-140).  The three covariances are one form over a point set p_i
+ * (actuators, or sub-apertures):
+ *     out[b][i][j] = sum_t w[b][t] F_kind(t)( |p_j - p_i + o[b][t]| ; x0, L0[b][t] )
+ * with F = dphi_lowpass (Cerr, compute_Cerr_cpu :145-186), dphi_highpass (Calias, compute_Calias :590-599 with
+ * compute_Calias_element_XX / _YY :633-700) or rodconan (dCmm, compute_dCmm_element :842-903).  F and the sum over the
+ * taps are evaluated in double, in the taps' order; out is rounded to float once.
+ *   n_max, batch_max    largest point set and most batch entries of one aomarl_groot_form call
+ *   m_max, k_max        aomarl_groot_sandwich: most rows of G and largest order of C (both 0: no sandwich workspace)
+ *   tabx, taby          HOST [10000]: the Ij0 table of starlord.tabulateIj0 (:56-72), x = e^t for t in [-4, 10]; copied */
+typedef struct {
+  int32_t n_max, batch_max, m_max, k_max;
+  const double *tabx, *taby;
+} aomarl_groot_desc;
+#define AOMARL_GROOT_CERR 0
+#define AOMARL_GROOT_CALIAS_XX 1
+#define AOMARL_GROOT_CALIAS_YY 2
+#define AOMARL_GROOT_DCMM_XX 3
+#define AOMARL_GROOT_DCMM_YY 4
+/* One model for `batch` atmospheres; all arrays HOST [batch][nlayers], read before the call returns.
+ *   CERR       w = (1 / r0)^(5/3) frac (lambda_tar / 2 pi)^2 per layer, (sx, sy) = vdt u(theta) + Htheta u(angleht),
+ *              vdt = speed ittime / gain (:152-170, :183-186), x0 = the actuator pitch (:160), L0 per layer
+ *   CALIAS_*   nlayers = 1, w = 1/2 (1 / r0)^(5/3) c^2 (h / 3)^2 (:562-563, :609), x0 = d the sub-aperture size, npts
+ *              the (odd) number of Simpson points (:612-630); sx, sy, L0 are not read
+ *   DCMM_*     w = frac scale (:827, :837), (sx, sy) = ws dt u(wd) (:859-860), x0 = d, L0 per layer */
+typedef struct {
+  int32_t model, batch, nlayers, npts;
+  double x0;
+  const double *w, *sx, *sy, *L0;
+} aomarl_groot_form_desc;
+typedef struct aomarl_groot aomarl_groot;
+/* Allocates the table, the tap buffers and the sandwich's workspace; no device or pinned memory is allocated afterwards
+ * (a form call builds its tap list in a host vector). */
+int aomarl_groot_create(const aomarl_groot_desc *desc, aomarl_groot **out);
+int aomarl_groot_destroy(aomarl_groot *g);
+/* px, py: DEVICE double [n], the points; out: DEVICE float, out[b * stride_o + i * ldo + j].  One thread owns one
+ * element and adds its taps in order: entry b of a batched call and the same atmosphere alone leave the same bits.
+ * Every w, sx, sy, L0 must be finite (refused by name otherwise).  Asynchronous on `stream`, except that a call first
+ * waits for the object's previous form call to finish, on whatever stream that ran: the object has one tap buffer.  The
+ * sandwich's workspace is not guarded in that way: use one stream per object for aomarl_groot_sandwich. */
+int aomarl_groot_form(aomarl_groot *g, const aomarl_groot_form_desc *f, const double *px, const double *py, int n,
+                      float *out, int ldo, long long stride_o, void *stream);
+/* out [m][ldo] (+)= G [m][ldg] . C [n][ldc] . G^T in fp32 (the projections of :200-209, :601-606): two products on the
+ * loop's fp32 matrix kernel, T = G C^T then out = G T^T; k splits are summed in a fixed order.  All DEVICE; G and C:
+ * 16-byte aligned, ldg and ldc multiples of 4.  accumulate != 0 adds to out.  Asynchronous on `stream`. */
+int aomarl_groot_sandwich(aomarl_groot *g, const float *G, int ldg, int m, const float *C, int ldc, int n, float *out,
+                          int ldo, int accumulate, void *stream);
 /* PSF window + phase variance of st->tar_phase as it stands (pending, like aomarl_target_psf) */
 int aomarl_target_psf_buffer(aomarl_ctx *ctx, aomarl_state *st, int env_begin, int env_count,
                              void *stream);

@@ -10,7 +10,11 @@ contributor variance (the diagonal of cov, microns^2), the correlation table, th
 Strehl and how far exp(-(variance of the sum + fitting)) closes on it.
 
 With --psf-rec the PSF of environment 0 is reconstructed from the covariance of its error buffers (ao_marl_amd.psf_rec,
-the reference's gamora.psf_rec_Vii) and its Strehl printed beside the loop's; --psf-rec-out FILE keeps otf2 and psf."""
+the reference's gamora.psf_rec_Vii) and its Strehl printed beside the loop's; --psf-rec-out FILE keeps otf2 and psf.
+
+With --groot the bandwidth (+ tomography) variance and the PSF Strehl that the GROOT model (ao_marl_amd.groot) predicts from
+wind, r0, L0, gain and guide-star offset alone are printed beside ROKET's measured ones for environment 0: the reference's
+groot.test_Cerr.  A comparison, not a check."""
 import argparse
 import os
 import sys
@@ -37,6 +41,8 @@ def main(argv=None):
     ap.add_argument("--save", default=None, help=".npz of the histories of environment 0")
     ap.add_argument("--psf-rec", action="store_true", help="reconstruct the long-exposure PSF of environment 0 (Vii)")
     ap.add_argument("--psf-rec-out", default=None, help=".npz for otftel, otf2 and psf of --psf-rec")
+    ap.add_argument("--groot", action="store_true", help="the GROOT model's bandwidth + tomography covariance and PSF "
+                    "beside ROKET's measured ones, environment 0 (groot.test_Cerr)")
     a = ap.parse_args(argv)
     from ao_marl_amd import roket
     from ao_marl_amd.env import VecAoEnv
@@ -58,7 +64,7 @@ def main(argv=None):
             sac.load_model(i, os.path.join(a.checkpoints, f))
         policy = sac.policy
     rk = roket.VecRoket(env, a.frames, a.preloop, policy=policy, gamma=a.gamma, accumulate_from=a.accumulate_from,
-                        keep_envs=(0,) if a.save or a.psf_rec else (), psf_ortho_envs=(0,) if a.psf_rec else ())
+                        keep_envs=(0,) if a.save or a.psf_rec or a.groot else (), psf_ortho_envs=(0,) if a.psf_rec else ())
     res = rk.run()
     names = res["contributors"]
     cov, cor = res["cov"].mean(axis=0), res["cor"].mean(axis=0)
@@ -97,6 +103,30 @@ def main(argv=None):
         if a.psf_rec_out:
             np.savez(a.psf_rec_out, otftel=otftel, otf2=otf2, psf=psf, psf_without_fitting=bare)
             print("otftel, otf2, psf -> %s" % a.psf_rec_out)
+    if a.groot:
+        # groot.test_Cerr (:215-246) without its plots: how well the model fits this simulator is a result, not a check
+        from ao_marl_amd import groot, psf_rec
+        d, rec = psf_rec.from_source(rk)
+        model = groot.GrootModel(rk)
+        measured = psf_rec.covmodes_from(d, 0, contributors=["bandwidth", "tomography"])
+        cerr = model.cerr()
+        sr = lambda c: float(rec.reconstruct(c)["strehl"])                         # noqa: E731
+        print("GROOT, environment 0 (variances in um^2, x %.4f for rad^2 at the target):" % k)
+        print("  bandwidth + tomography   ROKET trace %.6e   model trace %.6e   ratio %.3f" %
+              (np.trace(measured), np.trace(cerr), np.trace(cerr) / np.trace(measured)))
+        print("  largest mode             ROKET %.6e   model %.6e" % (np.diag(measured).max(), np.diag(cerr).max()))
+        print("  PSF of that covariance alone (no fitting): Strehl ROKET %.4f   model %.4f" % (sr(measured), sr(cerr)))
+        full = model.psf(env=0, rec=rec)
+        print("  model PSF (Cerr + measured noise + Calias, fitting OTF): Strehl %.4f   |   loop: SR long exposure %.4f" %
+              (full["strehl"], float(res["SR"][0])))
+        # the reference's Nact^-1 yields commands of unit-peak influence functions; this mirror's peak at unitpervolt
+        u = model.stroke_scale
+        if u is not None and u != 1.0:
+            print("  the mirror's unitpervolt puts the model's Cerr a factor %.4g below the commands' volts^2 (GrootModel."
+                  "stroke_scale); with cerr_scale = %.4g:" % (u, u))
+            print("  bandwidth + tomography   model trace %.6e   ratio to ROKET %.3f   Strehl of that covariance alone %.4f" %
+                  (np.trace(cerr) * u, np.trace(cerr) * u / np.trace(measured), sr(cerr * u)))
+            print("  model PSF: Strehl %.4f" % model.psf(env=0, rec=rec, cerr_scale=u)["strehl"])
     return res
 
 
