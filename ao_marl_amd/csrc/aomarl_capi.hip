@@ -188,7 +188,7 @@ int aomarl_set_precision(int mode) {
   g_cfg_epoch++;
   if (mode != AOMARL_PRECISION_F32 && mode != AOMARL_PRECISION_SPLIT_F16) return fail("set_precision: unknown mode %d", mode);
   g_precision = mode;
-  g_gemm_split_f16 = mode == AOMARL_PRECISION_SPLIT_F16;
+  g_gemm.split_f16 = mode == AOMARL_PRECISION_SPLIT_F16;
   return 0;
 }
 int aomarl_get_precision(void) { return g_precision; }

@@ -125,12 +125,13 @@ struct ExtrudeRun {          // one range of environments walking through a sequ
                            ops, Z, w.ldz, ZREF);
         LAUNCHCHK();
       }
-      int nsp = 0;
-      float pscale = 1.f;
-      launch_gemm_nt(ncol, dimc, K, 1.0f, Z, w.ldz, c->sys.layers[ref].AB, c->sys.layers[ref].ldab,
-                     0.0f, NEWL, w.ldn, s, WS, ws_floats, nullptr, &nsp,
-                     /* split-f16: stencil values (um) and N(0,1) draws x 2^8 */ true, 256.f, c->ab_scale[cls], &pscale,
-                     128, pick_n > 0 && pick_n < n ? pick_n * ops.nops : 0);
+      GemmArgs ga(ncol, dimc, K, 1.0f, Z, w.ldz, c->sys.layers[ref].AB, c->sys.layers[ref].ldab, 0.0f, NEWL, w.ldn, s);
+      ga.ws = WS; ga.ws_floats = ws_floats; ga.slabs_only = true;
+      ga.fast = true; ga.sa = 256.f; ga.sb = c->ab_scale[cls];    /* split-f16: stencil values (um) and N(0,1) draws x 2^8 */
+      ga.pick_M = pick_n > 0 && pick_n < n ? pick_n * ops.nops : 0;
+      const GemmDone gd = launch_gemm_nt(ga);
+      const int nsp = gd.slabs;
+      const float pscale = gd.slab_alpha;
       LAUNCHCHK();
       if (ordered) {
         int wrc = first_write_wait(c, s);

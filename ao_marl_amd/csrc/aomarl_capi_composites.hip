@@ -218,7 +218,7 @@ int aomarl_gemm_nt(int M, int N, int K, float alpha, const float *A, int lda, co
                    float beta, float *C, int ldc, void *stream) {
   if (!A || !B || !C) return fail("gemm_nt: null pointer");
   if (M < 0 || N < 0 || K < 1 || lda < K || ldb < K || ldc < N) return fail("gemm_nt: bad sizes (K must be at least 1)");
-  launch_gemm_nt(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, (hipStream_t)stream);
+  launch_gemm_nt(GemmArgs(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, (hipStream_t)stream));
   LAUNCHCHK();
   return 0;
 }
@@ -232,11 +232,12 @@ int aomarl_gemm_nt_split(int M, int N, int K, float alpha, const float *A, int l
     return fail("gemm_nt_split: operands must be 16-byte aligned with leading dimensions that are multiples of 4");
   auto pow2 = [](float v) { int e; return v > 0.f && frexpf(v, &e) == 0.5f; };
   if (!pow2(scale_a) || !pow2(scale_b)) return fail("gemm_nt_split: scales must be powers of two");
-  const bool keep = g_gemm_split_f16;
-  g_gemm_split_f16 = true;
-  launch_gemm_nt(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, (hipStream_t)stream, work, (size_t)std::max(0LL, work_floats),
-                 nullptr, nullptr, true, scale_a, scale_b);
-  g_gemm_split_f16 = keep;
+  GemmArgs ga(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, (hipStream_t)stream);
+  ga.ws = work; ga.ws_floats = (size_t)std::max(0LL, work_floats);
+  ga.fast = true; ga.sa = scale_a; ga.sb = scale_b;
+  GemmOptions opt = g_gemm;                      // this entry point IS the split-f16 kernel, whatever the option says
+  opt.split_f16 = true;
+  launch_gemm_nt(ga, opt);
   LAUNCHCHK();
   return 0;
 }
@@ -272,17 +273,16 @@ int aomarl_gemm_nt_probe(int M, int N, int K, float alpha, const float *A, int l
   ep.amode_inv = probe->epi_amode_inv; ep.freedom = probe->epi_freedom;
   GemmForce f;
   memset(&f, 0, sizeof(f));
-  f.kernel = probe->kernel; f.wm = probe->wm; f.wn = probe->wn; f.ksplit = probe->ksplit; f.xcd = probe->xcd;
-  int nsplit = 0;
-  float alpha_out = alpha;
-  float *ws = work_floats > 0 ? work : nullptr;
-  const bool fused = launch_gemm_nt(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, (hipStream_t)stream, ws, (size_t)work_floats,
-                                    probe->epi_mode ? &ep : nullptr, probe->slabs_only ? &nsplit : nullptr, false, sa, sb,
-                                    &alpha_out, 128, probe->pick_M, &f);
+  f.in.kernel = probe->kernel; f.in.wm = probe->wm; f.in.wn = probe->wn; f.in.ksplit = probe->ksplit; f.in.xcd = probe->xcd;
+  GemmArgs ga(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, (hipStream_t)stream);
+  ga.ws = work_floats > 0 ? work : nullptr; ga.ws_floats = (size_t)work_floats;
+  ga.epi = probe->epi_mode ? &ep : nullptr; ga.slabs_only = probe->slabs_only != 0;
+  ga.sa = sa; ga.sb = sb; ga.pick_M = probe->pick_M; ga.force = &f;
+  const GemmDone gd = launch_gemm_nt(ga);
   if (f.error) return fail("gemm_nt_probe: refused %s", f.error);
   LAUNCHCHK();
   probe->r_kernel = f.r_kernel; probe->r_wm = f.r_wm; probe->r_wn = f.r_wn; probe->r_nz = f.r_nz; probe->r_kchunk = f.r_kchunk;
-  probe->r_slabs = nsplit; probe->r_alpha = alpha_out; probe->r_fused = fused ? 1 : 0;
+  probe->r_slabs = gd.slabs; probe->r_alpha = gd.slab_alpha; probe->r_fused = gd.epi_done ? 1 : 0;
   probe->p_wm = f.pick.wm; probe->p_wn = f.pick.wn; probe->p_nz = f.pick.nz; probe->p_kchunk = f.pick.kchunk;
   return 0;
 }

@@ -113,15 +113,17 @@ int aomarl_geo_control(aomarl_ctx *c, aomarl_state *st, int b, int n, float *wor
                               (long long)gw * gh, 0, stream);
   if (rc) return rc;
   // R3[e][k] = sum_p phi[e][p] planes[k][p]   (TT0, TT1, 1)
-  launch_gemm_nt(n, 3, pd * pd, 1.0f, phi, pd * pd, c->geoPlanes, pd * pd, 0.0f, R3, 4, s, work + g.GEMM,
-                 g.gemm_floats);
+  GemmArgs g3(n, 3, pd * pd, 1.0f, phi, pd * pd, c->geoPlanes, pd * pd, 0.0f, R3, 4, s);
+  g3.ws = work + g.GEMM; g3.ws_floats = g.gemm_floats;
+  launch_gemm_nt(g3);
   LAUNCHCHK();
   hipLaunchKernelGGL(k_geo_assemble, dim3((c->geo_ldr + 255) / 256, n), dim3(256), 0, s, na, c->geo_npzt,
                      c->geo_ldr, gw * gh, c->geoMap, LAT, R3, R);
   LAUNCHCHK();
   // com[e] = W . r[e]
-  launch_gemm_nt(n, na, na + 1, 1.0f, R, c->geo_ldr, c->geoW, c->geo_ldw, 0.0f,
-                 st->com + (size_t)b * st->ld_actu, st->ld_actu, s, work + g.GEMM, g.gemm_floats);
+  GemmArgs gcom(n, na, na + 1, 1.0f, R, c->geo_ldr, c->geoW, c->geo_ldw, 0.0f, st->com + (size_t)b * st->ld_actu, st->ld_actu, s);
+  gcom.ws = work + g.GEMM; gcom.ws_floats = g.gemm_floats;
+  launch_gemm_nt(gcom);
   LAUNCHCHK();
   return 0;
 }
@@ -206,13 +208,13 @@ int aomarl_target_image(aomarl_ctx *c, aomarl_state *st, int b, int n, float *ou
     hipLaunchKernelGGL(k_timg_amp, dim3((pd * pd + 255) / 256), dim3(256), 0, s, ph, c->sys.spupil, c->sys.tar_inv_lambda, amp, pd);
     LAUNCHCHK();
     // pass 1: X[(re | im, kx)][y] = W1 . amp^T
-    launch_gemm_nt(2 * np, pd, 2 * pd, 1.0f, W1, 2 * pd, amp, 2 * pd, 0.0f, X, pd, s);
+    launch_gemm_nt(GemmArgs(2 * np, pd, 2 * pd, 1.0f, W1, 2 * pd, amp, 2 * pd, 0.0f, X, pd, s));
     // pass 2: Y[ky][kx]:  Yr = Wc Xr^T + Ws Xi^T,  Yi = Wc Xi^T - Ws Xr^T
     const float *Xr = X, *Xi = X + (size_t)np * pd;
-    launch_gemm_nt(np, np, pd, 1.0f, Wc, pd, Xr, pd, 0.0f, Yr, np, s);
-    launch_gemm_nt(np, np, pd, 1.0f, Ws, pd, Xi, pd, 1.0f, Yr, np, s);
-    launch_gemm_nt(np, np, pd, 1.0f, Wc, pd, Xi, pd, 0.0f, Yi, np, s);
-    launch_gemm_nt(np, np, pd, -1.0f, Ws, pd, Xr, pd, 1.0f, Yi, np, s);
+    launch_gemm_nt(GemmArgs(np, np, pd, 1.0f, Wc, pd, Xr, pd, 0.0f, Yr, np, s));
+    launch_gemm_nt(GemmArgs(np, np, pd, 1.0f, Ws, pd, Xi, pd, 1.0f, Yr, np, s));
+    launch_gemm_nt(GemmArgs(np, np, pd, 1.0f, Wc, pd, Xi, pd, 0.0f, Yi, np, s));
+    launch_gemm_nt(GemmArgs(np, np, pd, -1.0f, Ws, pd, Xr, pd, 1.0f, Yi, np, s));
     LAUNCHCHK();
     hipLaunchKernelGGL(k_timg_abs2, dim3((unsigned)(((long long)np * np + 255) / 256)), dim3(256), 0, s, Yr, Yi,
                        out + (size_t)(e - b) * np * np, (long long)np * np);

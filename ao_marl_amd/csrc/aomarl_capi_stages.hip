@@ -55,9 +55,9 @@ int aomarl_set_option(aomarl_ctx *c, const char *name, int value) {
     g_gemm_kgroups = value;
     return 0;
   }
-  if (!strcmp(name, "gemm_xcd_map")) { g_gemm_xcd = value != 0; return 0; }   // process-wide
-  if (!strcmp(name, "gemm_target_blocks")) { g_gemm_target_blocks = value > 0 ? value : 0; return 0; }   // process-wide
-  if (!strcmp(name, "gemm_split_f16")) { g_gemm_split_f16 = value != 0; return 0; }          // process-wide
+  if (!strcmp(name, "gemm_xcd_map")) { g_gemm.xcd = value != 0; return 0; }   // process-wide
+  if (!strcmp(name, "gemm_target_blocks")) { g_gemm.target_blocks = value > 0 ? value : 0; return 0; }   // process-wide
+  if (!strcmp(name, "gemm_split_f16")) { g_gemm.split_f16 = value != 0; return 0; }          // process-wide
   if (!strcmp(name, "precision")) return aomarl_set_precision(value);                        // process-wide
   if (!c) return fail("set_option: null context");
   if (!strcmp(name, "force_generic_dm")) { c->force_generic_dm = value != 0; return 0; }
@@ -242,9 +242,11 @@ int aomarl_do_control(aomarl_ctx *c, aomarl_state *st, int b, int n, void *strea
     return fail("do_control: %d per-environment gains set, the state has %d environments", c->env_gain_n, st->nenv);
   ep.mode = 1; ep.com = st->com + (size_t)b * st->ld_actu; ep.ldcom = st->ld_actu; ep.gain = c->gain;
   ep.gain_row = c->env_gain ? c->env_gain + b : nullptr;
-  const bool fused = launch_gemm_nt(n, na, nsl, -1.0f, st->slopes + (size_t)b * nsl, nsl, c->cmat, c->ld_cmat, 0.0f,
-                                    st->err + (size_t)b * st->ld_actu, st->ld_actu, s, st->work + w.GEMM,
-                                    w.gemm_floats, &ep, nullptr, /* slopes (arcsec): unscaled, saturation only beyond 65504" */ true, 1.f, c->cmat_scale, nullptr, 288);
+  GemmArgs ga(n, na, nsl, -1.0f, st->slopes + (size_t)b * nsl, nsl, c->cmat, c->ld_cmat, 0.0f,
+              st->err + (size_t)b * st->ld_actu, st->ld_actu, s);
+  ga.ws = st->work + w.GEMM; ga.ws_floats = w.gemm_floats; ga.epi = &ep; ga.min_chunk = 288;
+  ga.fast = true; ga.sb = c->cmat_scale;                     /* slopes (arcsec): unscaled, saturation only beyond 65504" */
+  const bool fused = launch_gemm_nt(ga).epi_done;
   LAUNCHCHK();
   if (!fused) {
     hipLaunchKernelGGL(k_integrate, dim3((na + 255) / 256, n), dim3(256), 0, s, st->com, st->err, na, st->ld_actu, c->gain, b, c->env_gain);
@@ -273,8 +275,10 @@ int aomarl_volts2modes(aomarl_ctx *c, aomarl_state *st, int nrows, const float *
   float *ws = nullptr;
   size_t wsn = 0;
   if (st && st->work) { Work w = work_layout(c, st->nenv); ws = st->work + w.GEMM; wsn = w.gemm_floats; }
-  launch_gemm_nt(nrows, c->nmodes, c->sys.nactu, 1.0f, vec, ldvec, c->v2m, c->ld_v2m, 0.0f,
-                 modes, c->nmodes, (hipStream_t)stream, ws, wsn, nullptr, nullptr, /* volts */ true, 1.f, c->v2m_scale, nullptr, 288);
+  GemmArgs ga(nrows, c->nmodes, c->sys.nactu, 1.0f, vec, ldvec, c->v2m, c->ld_v2m, 0.0f, modes, c->nmodes, (hipStream_t)stream);
+  ga.ws = ws; ga.ws_floats = wsn; ga.min_chunk = 288;
+  ga.fast = true; ga.sb = c->v2m_scale;                      /* volts */
+  launch_gemm_nt(ga);
   LAUNCHCHK();
   return 0;
 }
@@ -288,9 +292,11 @@ int aomarl_slopes2modes(aomarl_ctx *c, aomarl_state *st, int b, int n, float *mo
   Work w = work_layout(c, st->nenv);
   const int nsl = c->sys.nslope, ld = (nsl + 3) & ~3;
   // residual modes = v2m . err = -(v2m . cmat) . slopes
-  launch_gemm_nt(n, c->s2m_nmodes, nsl, -1.0f, st->slopes + (size_t)b * nsl, nsl, c->s2m, ld, 0.0f, modes,
-                 c->s2m_nmodes, (hipStream_t)stream, st->work + w.GEMM, w.gemm_floats, nullptr, nullptr,
-                 /* slopes (arcsec), unscaled */ true, 1.f, c->s2m_scale, nullptr, 288);
+  GemmArgs ga(n, c->s2m_nmodes, nsl, -1.0f, st->slopes + (size_t)b * nsl, nsl, c->s2m, ld, 0.0f, modes, c->s2m_nmodes,
+              (hipStream_t)stream);
+  ga.ws = st->work + w.GEMM; ga.ws_floats = w.gemm_floats; ga.min_chunk = 288;
+  ga.fast = true; ga.sb = c->s2m_scale;                      /* slopes (arcsec), unscaled */
+  launch_gemm_nt(ga);
   LAUNCHCHK();
   return 0;
 }
@@ -309,15 +315,19 @@ int aomarl_rl_control(aomarl_ctx *c, aomarl_state *st, int b, int n, const float
   float *com = st->com + (size_t)b * st->ld_actu;
   GemmEpi ep = {};
   ep.mode = 2; ep.action = action; ep.nact = c->nact; ep.amode_inv = c->amode_inv; ep.freedom = c->freedom;
-  const bool fused = launch_gemm_nt(n, nm, na, 1.0f, com, st->ld_actu, c->v2m, c->ld_v2m, 0.0f, modes, w.ldm, s,
-                                    st->work + w.GEMM, w.gemm_floats, &ep, nullptr, true, 1.f, c->v2m_scale, nullptr, 288);
+  GemmArgs gv(n, nm, na, 1.0f, com, st->ld_actu, c->v2m, c->ld_v2m, 0.0f, modes, w.ldm, s);
+  gv.ws = st->work + w.GEMM; gv.ws_floats = w.gemm_floats; gv.epi = &ep; gv.min_chunk = 288;
+  gv.fast = true; gv.sb = c->v2m_scale;                      /* volts */
+  const bool fused = launch_gemm_nt(gv).epi_done;
   LAUNCHCHK();
   if (!fused) {
     hipLaunchKernelGGL(k_modal_add, dim3((c->nact + 255) / 256, n), dim3(256), 0, s, modes, w.ldm, action, c->nact, c->amodes, c->freedom);
     LAUNCHCHK();
   }
-  launch_gemm_nt(n, na, nm, 1.0f, modes, w.ldm, c->m2v, c->ld_m2v, 0.0f, com, st->ld_actu, s, st->work + w.GEMM, w.gemm_floats,
-                 nullptr, nullptr, /* Btt coordinates x 2^4 */ true, 16.f, c->m2v_scale, nullptr, 288);
+  GemmArgs gm(n, na, nm, 1.0f, modes, w.ldm, c->m2v, c->ld_m2v, 0.0f, com, st->ld_actu, s);
+  gm.ws = st->work + w.GEMM; gm.ws_floats = w.gemm_floats; gm.min_chunk = 288;
+  gm.fast = true; gm.sa = 16.f; gm.sb = c->m2v_scale;        /* Btt coordinates x 2^4 */
+  launch_gemm_nt(gm);
   LAUNCHCHK();
   return 0;
 }
@@ -386,9 +396,10 @@ int aomarl_rl_control_modes(aomarl_ctx *c, aomarl_state *st, int b, int n, const
   hipLaunchKernelGGL(k_modal_compose, dim3((nm + 255) / 256, n), dim3(256), 0, s, nm, m0, m1, g, action,
                      c->nact, c->amode_inv, c->freedom, modes, w.ldm, modes_out);
   LAUNCHCHK();
-  launch_gemm_nt(n, na, nm, 1.0f, modes, w.ldm, c->m2v, c->ld_m2v, 0.0f,
-                 st->com + (size_t)b * st->ld_actu, st->ld_actu, s, st->work + w.GEMM, w.gemm_floats,
-                 nullptr, nullptr, /* Btt coordinates x 2^4 */ true, 16.f, c->m2v_scale, nullptr, 288);
+  GemmArgs ga(n, na, nm, 1.0f, modes, w.ldm, c->m2v, c->ld_m2v, 0.0f, st->com + (size_t)b * st->ld_actu, st->ld_actu, s);
+  ga.ws = st->work + w.GEMM; ga.ws_floats = w.gemm_floats; ga.min_chunk = 288;
+  ga.fast = true; ga.sa = 16.f; ga.sb = c->m2v_scale;        /* Btt coordinates x 2^4 */
+  launch_gemm_nt(ga);
   LAUNCHCHK();
   return 0;
 }

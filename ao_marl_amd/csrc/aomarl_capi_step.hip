@@ -304,10 +304,12 @@ static int env_step_head_fused(aomarl_ctx *c, aomarl_state *st, aomarl_state *st
                      g->res_modes, gain, action, c->nact, c->amode_inv, c->freedom, modes, w.ldm, mnew, cx,
                      g->n_agents, g->lohi, g->reward_factor, reward_out);
   LAUNCHCHK();
-  int nsp = 0;
-  float alpha = 1.f;
-  launch_gemm_nt(n, na, nm, 1.0f, modes, w.ldm, c->m2v, c->ld_m2v, 0.0f, st->com, st->ld_actu, s,
-                 st->work + w.GEMM, w.gemm_floats, nullptr, &nsp, true, 16.f, c->m2v_scale, &alpha, 288);
+  GemmArgs ga(n, na, nm, 1.0f, modes, w.ldm, c->m2v, c->ld_m2v, 0.0f, st->com, st->ld_actu, s);
+  ga.ws = st->work + w.GEMM; ga.ws_floats = w.gemm_floats; ga.slabs_only = true; ga.min_chunk = 288;
+  ga.fast = true; ga.sa = 16.f; ga.sb = c->m2v_scale;      /* Btt coordinates x 2^4 */
+  const GemmDone gd = launch_gemm_nt(ga);
+  const int nsp = gd.slabs;
+  const float alpha = gd.slab_alpha;
   LAUNCHCHK();
   const float d = c->delay;
   float wa, wb, wc;
@@ -387,21 +389,20 @@ static int env_step_tail(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, bo
   }
   AssemblePart part = {nullptr, 0, 0, 1.f, nullptr};
   if (s2m_view) {
-    int nsp = 0;
-    float alpha = -1.f;
     const int nsl = c->sys.nslope;
-    launch_gemm_nt(n, nm, nsl, -1.0f, s2m_view->slopes, nsl, c->s2m, c->ld_cmat, 0.0f, g->res_modes, nm, s,
-                   st->work + w.GEMM, w.gemm_floats, nullptr, &nsp, /* slopes (arcsec), unscaled */ true, 1.f, c->s2m_scale,
-                   &alpha, 288);
+    GemmArgs ga(n, nm, nsl, -1.0f, s2m_view->slopes, nsl, c->s2m, c->ld_cmat, 0.0f, g->res_modes, nm, s);
+    ga.ws = st->work + w.GEMM; ga.ws_floats = w.gemm_floats; ga.slabs_only = true; ga.min_chunk = 288;
+    ga.fast = true; ga.sb = c->s2m_scale;                    /* slopes (arcsec), unscaled */
+    const GemmDone gd = launch_gemm_nt(ga);
     LAUNCHCHK();
-    if (nsp > 0) { part.part = st->work + w.GEMM; part.nsplit = nsp; part.pn = nm; part.alpha = alpha; part.sum_out = g->res_modes; }
+    if (gd.slabs > 0) { part.part = st->work + w.GEMM; part.nsplit = gd.slabs; part.pn = nm; part.alpha = gd.slab_alpha; part.sum_out = g->res_modes; }
   } else if (fused) {
-    int nsp = 0;
-    float alpha = 1.f;
-    launch_gemm_nt(n, nm, na, 1.0f, st->err, st->ld_actu, c->v2m, c->ld_v2m, 0.0f, g->res_modes, nm, s,
-                   st->work + w.GEMM, w.gemm_floats, nullptr, &nsp, /* volts */ true, 1.f, c->v2m_scale, &alpha, 288);
+    GemmArgs ga(n, nm, na, 1.0f, st->err, st->ld_actu, c->v2m, c->ld_v2m, 0.0f, g->res_modes, nm, s);
+    ga.ws = st->work + w.GEMM; ga.ws_floats = w.gemm_floats; ga.slabs_only = true; ga.min_chunk = 288;
+    ga.fast = true; ga.sb = c->v2m_scale;                    /* volts */
+    const GemmDone gd = launch_gemm_nt(ga);
     LAUNCHCHK();
-    if (nsp > 0) { part.part = st->work + w.GEMM; part.nsplit = nsp; part.pn = nm; part.alpha = alpha; part.sum_out = g->res_modes; }
+    if (gd.slabs > 0) { part.part = st->work + w.GEMM; part.nsplit = gd.slabs; part.pn = nm; part.alpha = gd.slab_alpha; part.sum_out = g->res_modes; }
   } else {
     rc = aomarl_volts2modes(c, st, n, st->err, st->ld_actu, g->res_modes, stream);
     if (rc) return rc;
@@ -798,9 +799,9 @@ int aomarl_env_step(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const f
   kp(action); kp(state_out); kp(reward_out); kp(stream);
   kp(g->sel); kp(g->mean_dm); kp(g->std_dm); kp(g->mean_res); kp(g->std_res); kp(g->lohi); kp(g->modes_ring); kp(g->res_modes);
   kp(g->denoiser); kp(c->cmat); kp(c->v2m); kp(c->m2v); kp(c->freedom); kp(c->amode_inv);
-  key.push_back(n); key.push_back(g_precision); key.push_back(g_gemm_split_f16 ? 1 : 0); key.push_back(c->dft_mode);
+  key.push_back(n); key.push_back(g_precision); key.push_back(g_gemm.split_f16 ? 1 : 0); key.push_back(c->dft_mode);
   key.push_back(pf ? 1 : 0); key.push_back(c->small_move); key.push_back(c->small_chain); key.push_back(c->residual_shortcut);
-  key.push_back(c->defer_dm_shape ? 1 : 0); key.push_back(g_gemm_target_blocks); key.push_back(c->fused_debug);
+  key.push_back(c->defer_dm_shape ? 1 : 0); key.push_back(g_gemm.target_blocks); key.push_back(c->fused_debug);
   { int gi; memcpy(&gi, &c->gain, sizeof(gi)); key.push_back(gi); }
   key.push_back((long long)c->cfg_epoch); key.push_back((long long)g_cfg_epoch);
   aomarl_ctx::StepGraph *hit = nullptr;
@@ -829,7 +830,7 @@ int aomarl_env_step(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const f
     return 0;
   }
   // ---- capture
-  if (g_gemm_split_f16) (void)gemm_sat_counter();          // nothing may allocate during the capture
+  if (g_gemm.split_f16) (void)gemm_sat_counter();          // nothing may allocate during the capture
   if (c->graphs.size() >= 256) {                            // a caller that cycles through many buffers: start over
     for (auto &sg : c->graphs) { (void)hipGraphExecDestroy(sg.exec); (void)hipGraphDestroy(sg.graph); }
     c->graphs.clear();

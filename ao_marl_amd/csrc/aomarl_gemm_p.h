@@ -7,8 +7,8 @@
 // (shesha/supervisor/components/rtcCompass.py:527-547), and the two Btt projections v2m / m2v
 // (src/reinforcement_learning/.../rlSupervisor.py:784-818).  Each is 0.8 - 2 GFLOP: a handful of output tiles for
 // 256 CUs, so K is split and the consumers sum the partial slabs P[z][M][N] (k_gemm_reduce_epi, the extrusion
-// scatter, the delay line, the state assembly).  What this kernel changes against k_gemm_nt2 (64x64 tiles, one
-// 32x32x2 accumulator per wave, a barrier every 16 matrix instructions, 84 - 396 workgroups):
+// scatter, the delay line, the state assembly).  What this kernel changes against the pipelined 64x64 kernel it
+// replaced (since retired: one 32x32x2 accumulator per wave, a barrier every 16 matrix instructions, 84 - 396 workgroups):
 //   * the grid is CHOSEN so that every CU gets the same number of workgroups (gemm_p_pick: wave tile, block tile
 //     and k-chunk from a menu, cost = the busiest CU's matrix time + the partial slabs' traffic);
 //   * a wave owns (16 WM) x (16 WN) outputs = WM x WN independent v_mfma_f32_16x16x4_f32 accumulators (12 - 16

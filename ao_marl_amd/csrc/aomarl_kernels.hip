@@ -40,484 +40,11 @@ __device__ __forceinline__ void add4_ring(float acc[4], const float *row, int px
   add4(acc, row + px);
 }
 
-// =============================================================================================
-// fp32 GEMM  C[M][N] = alpha * A[M][K] . B[N][K]^T + beta * C     (both operands K-contiguous), ANY alignment:
-// the fallback behind k_gemm_p (aomarl_gemm_p.h), which wants 16-byte aligned rows.  Element-wise loads,
-// 256 threads = 4 waves in 2x2, block tile 64x64, one v_mfma_f32_32x32x2_f32 accumulator/wave.
-// =============================================================================================
-__global__ __launch_bounds__(256) void k_gemm_nt(int M, int N, int K, float alpha,
-                                                 const float *__restrict__ A, int lda,
-                                                 const float *__restrict__ B, int ldb, float beta,
-                                                 float *__restrict__ C, int ldc, int kchunk,
-                                                 float *__restrict__ P) {
-  // blockIdx.z = K split: the block reduces k in [z*kchunk, min(K, (z+1)*kchunk)); with more than
-  // one split the raw partial tile goes to P[z][M][N] and k_gemm_reduce finishes (deterministic)
-  __shared__ float As[64][17];
-  __shared__ float Bs[64][17];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wm = wv >> 1, wn = wv & 1;
-  const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
-  const int kb = blockIdx.z * kchunk, ke = min(K, kb + kchunk);
-  f32x16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; i++) acc[i] = 0.f;
-  const int lr = tid >> 2, lc = (tid & 3) * 4;
-  const int gm = m0 + lr, gn = n0 + lr;
-  const float *pa = A + (long long)gm * lda;
-  const float *pb = B + (long long)gn * ldb;
-  for (int k0 = kb; k0 < ke; k0 += 16) {
-    float va[4] = {0.f, 0.f, 0.f, 0.f}, vb[4] = {0.f, 0.f, 0.f, 0.f};
-    const int gk = k0 + lc;
-    if (gm < M) {
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (gk + j < ke) va[j] = pa[gk + j];
-    }
-    if (gn < N) {
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (gk + j < ke) vb[j] = pb[gk + j];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      As[lr][lc + j] = va[j];
-      Bs[lr][lc + j] = vb[j];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < 8; ks++) {
-      float a = As[wm * 32 + (lane & 31)][2 * ks + (lane >> 5)];
-      float b = Bs[wn * 32 + (lane & 31)][2 * ks + (lane >> 5)];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  const int col = n0 + wn * 32 + (lane & 31);
-  const bool split = gridDim.z > 1;
-#pragma unroll
-  for (int r = 0; r < 16; r++) {
-    int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    if (row < M && col < N) {
-      if (split) {
-        P[((long long)blockIdx.z * M + row) * N + col] = acc[r];
-      } else {
-        float *c = C + (long long)row * ldc + col;
-        float v = alpha * acc[r];
-        if (beta != 0.f) v += beta * (*c);
-        *c = v;
-      }
-    }
-  }
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// Pipelined variant (operands 16-byte aligned, lda / ldb multiples of 4): block tile 64 x 64 x 32,
-// double-buffered LDS (one barrier per k-tile), the global loads of tile k+1 are issued before the
-// MFMAs of tile k.  K order inside a tile is permuted so that every lane reads its 16 k-values of
-// a row as four 128-bit LDS reads: MFMA number i of the tile uses k = 16 (lane >> 5) + i for both
-// operands (any order is fine as long as A and B agree).  Row stride 36 floats: the 16 lanes of
-// a 128-bit read pass hit 64 distinct banks.
-// ---------------------------------------------------------------------------------------------
-#define G2_LD 36
-
-
-// ---------------------------------------------------------------------------------------------
-// The same GEMM on the f16 matrix pipe with SPLIT operands: every fp32 value v is carried as
-// hi = f16(v), lo = f16(v - hi), both rounded to nearest (23 significant bits, unbiased) and a product
-// as hi.hi + lo.hi + hi.lo with fp32 accumulation (lo.lo, <= 2^-24 of a product, dropped): three v_mfma_f32_32x32x16_f16 of 32 cycles
-// each per 16 k against sixteen 64-cycle v_mfma_f32_32x32x2_f32 (fp32 matrix instructions run at the
-// packed-fp32 vector rate on this chip) -- 10x less matrix-pipe time; what is left is the splitting
-// (2 vector instructions per element as it is staged into LDS) and the LDS traffic.
-// Operands stay fp32 in memory, same interface as k_gemm_nt plus a power-of-two scale per operand
-// (sa, sb; applied as the values are staged, undone through alpha): the scaled values must stay
-// below 65504 (they saturate above) and lose low bits of `lo` below 6e-5 (absolute error <= 3e-8
-// of the scaled value).  gemm_scale() picks the scale of a static matrix from its largest entry.
-// LDS: hi and lo planes of the A and B tiles as f16, [row][32 k] with a row stride of 40 halfs (a
-// 16-lane pass of a 128-bit read -- 8 k of one row per lane -- covers the 64 banks exactly once).
-// ---------------------------------------------------------------------------------------------
-#define GH_LD 40
-typedef _Float16 hx4 __attribute__((ext_vector_type(4)));
-// round-to-nearest-even pair (v_cvt_pk_f16_f32): unbiased, unlike the truncating v_cvt_pkrtz -- a GEMM
-// adds thousands of products, a truncation bias would add up linearly
-typedef float fx2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ hx2 cvt_rn2(float a, float b) {
-  const fx2 v = {a, b};
-  return __builtin_convertvector(v, hx2);
-}
-__device__ __forceinline__ void gh_split(float4 v, const float scale, hx4 &hi, hx4 &lo, float &amax) {
-  // power of two: exact; clamped to the f16 range (a value beyond it -- a centroid whose total flux
-  // came out ~0 -- saturates instead of turning into inf - inf = NaN).  amax: largest scaled magnitude this
-  // thread staged; the kernel counts the threads that saw one above the range (aomarl_gemm_saturated)
-  v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale;
-  amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-  v.x = __builtin_amdgcn_fmed3f(v.x, -65504.f, 65504.f); v.y = __builtin_amdgcn_fmed3f(v.y, -65504.f, 65504.f);
-  v.z = __builtin_amdgcn_fmed3f(v.z, -65504.f, 65504.f); v.w = __builtin_amdgcn_fmed3f(v.w, -65504.f, 65504.f);
-  const hx2 h01 = cvt_rn2(v.x, v.y), h23 = cvt_rn2(v.z, v.w);
-  const hx2 l01 = cvt_rn2(sub_lo(h01, v.x), sub_hi(h01, v.y));   // |v - hi| <= 2^-12 |v|, lo keeps 11 bits of it
-  const hx2 l23 = cvt_rn2(sub_lo(h23, v.z), sub_hi(h23, v.w));
-  hi = hx4{h01[0], h01[1], h23[0], h23[1]};
-  lo = hx4{l01[0], l01[1], l23[0], l23[1]};
-}
-
-// Three k-tiles of global loads are in flight per thread (register stages, loop unrolled by three):
-// with the 10-20 k-tiles a split-K block walks, one tile ahead left the loop waiting for L2 / HBM on
-// every iteration.  The loop body has NO branch around a load and no select on a load's result: the
-// loads are unconditional (addresses clamped into the row; a tile past the end of the chunk is masked
-// to zero as it is staged into LDS, so the loop simply runs whole groups of three tiles) -- with
-// either, the compiler waits for the data where it is loaded and the three stages collapse into one
-// (3 000 lines of branchy ISA and 20 us per call; measured).  Scheduling barriers keep the loads where
-// they are written.  Callers make the chunk a multiple of 96 so that only the last chunk has padding.
-__device__ __forceinline__ void gh_mainloop(const float *__restrict__ A, int lda,
-                                            const float *__restrict__ B, int ldb, int M, int N,
-                                            int m0, int n0, int kb, int ke, _Float16 *S, f32x16 &acc,
-                                            const float sa, const float sb, float &amax) {
-  // S: [2 buffers][4 planes: A hi, A lo, B hi, B lo][64 rows][GH_LD]
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wm = wv >> 1, wn = wv & 1;
-  const int lr = tid >> 3, lc = (tid & 7) * 4;
-  const float *pa0 = A + (long long)min(m0 + lr, M - 1) * lda;
-  const float *pa1 = A + (long long)min(m0 + lr + 32, M - 1) * lda;
-  const float *pb0 = B + (long long)min(n0 + lr, N - 1) * ldb;
-  const float *pb1 = B + (long long)min(n0 + lr + 32, N - 1) * ldb;
-  const int klast = (ke - 1) & ~3;               // last 16-byte group that holds a valid element (lda, ldb >= its end)
-  constexpr int ST = 3;                          // register stages
-  float4 ra0[ST], ra1[ST], rb0[ST], rb1[ST];
-  auto gload = [&](int k0, int st) {             // st: compile-time after unrolling
-    const int k = min(k0 + lc, klast);
-    ra0[st] = *reinterpret_cast<const float4 *>(pa0 + k); ra1[st] = *reinterpret_cast<const float4 *>(pa1 + k);
-    rb0[st] = *reinterpret_cast<const float4 *>(pb0 + k); rb1[st] = *reinterpret_cast<const float4 *>(pb1 + k);
-  };
-  constexpr int PL = 64 * GH_LD;                 // halfs per plane
-  auto lstore = [&](int buf, int st, int k0) {
-    _Float16 *s = S + buf * 4 * PL;
-    float4 a0 = ra0[st], a1 = ra1[st], b0 = rb0[st], b1 = rb1[st];
-    if (k0 + 32 > ke) {                          // wave-uniform: the tile crosses the end of the chunk
-      const int k = k0 + lc;
-      const bool m0_ = k < ke, m1_ = k + 1 < ke, m2_ = k + 2 < ke, m3_ = k + 3 < ke;
-      auto msk = [&](float4 &v) { v.x = m0_ ? v.x : 0.f; v.y = m1_ ? v.y : 0.f; v.z = m2_ ? v.z : 0.f; v.w = m3_ ? v.w : 0.f; };
-      msk(a0); msk(a1); msk(b0); msk(b1);
-    }
-    hx4 h, l;
-    gh_split(a0, sa, h, l, amax);
-    *reinterpret_cast<hx4 *>(s + lr * GH_LD + lc) = h; *reinterpret_cast<hx4 *>(s + PL + lr * GH_LD + lc) = l;
-    gh_split(a1, sa, h, l, amax);
-    *reinterpret_cast<hx4 *>(s + (lr + 32) * GH_LD + lc) = h; *reinterpret_cast<hx4 *>(s + PL + (lr + 32) * GH_LD + lc) = l;
-    gh_split(b0, sb, h, l, amax);
-    *reinterpret_cast<hx4 *>(s + 2 * PL + lr * GH_LD + lc) = h; *reinterpret_cast<hx4 *>(s + 3 * PL + lr * GH_LD + lc) = l;
-    gh_split(b1, sb, h, l, amax);
-    *reinterpret_cast<hx4 *>(s + 2 * PL + (lr + 32) * GH_LD + lc) = h; *reinterpret_cast<hx4 *>(s + 3 * PL + (lr + 32) * GH_LD + lc) = l;
-  };
-  // operand of lane l for k-chunk c (16 k): row (l & 31) of the wave's 32, k = 16 c + 8 (l >> 5) .. + 7
-  const int ro = (lane & 31) * GH_LD + 8 * (lane >> 5);
-#pragma unroll
-  for (int st = 0; st < ST; st++) gload(kb + 32 * st, st);
-  __builtin_amdgcn_sched_barrier(0);
-  lstore(0, 0, kb);
-  gload(kb + 32 * ST, 0);
-  __syncthreads();
-  int buf = 0;
-  for (int k0 = kb; k0 < ke; k0 += 32 * ST) {
-#pragma unroll
-    for (int u = 0; u < ST; u++) {
-      const int kc = k0 + 32 * u;                // the tile in LDS buffer `buf` (all zeros past the end)
-      // tile kc + 32 sits in register stage (u + 1) % ST: split it into the other LDS buffer, then
-      // reuse that stage for tile kc + 32 (ST + 1); only then the matrix instructions on this tile
-      lstore(buf ^ 1, (u + 1) % ST, kc + 32);
-      gload(kc + 32 * (ST + 1), (u + 1) % ST);
-      __builtin_amdgcn_sched_barrier(0);
-      const _Float16 *s = S + buf * 4 * PL;
-      const _Float16 *ah = s + wm * 32 * GH_LD + ro, *al = ah + PL;
-      const _Float16 *bh = s + 2 * PL + wn * 32 * GH_LD + ro, *bl = bh + PL;
-#pragma unroll
-      for (int cch = 0; cch < 2; cch++) {
-        const hx8 Ah = *reinterpret_cast<const hx8 *>(ah + 16 * cch), Al = *reinterpret_cast<const hx8 *>(al + 16 * cch);
-        const hx8 Bh = *reinterpret_cast<const hx8 *>(bh + 16 * cch), Bl = *reinterpret_cast<const hx8 *>(bl + 16 * cch);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl, acc, 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      __syncthreads();
-      buf ^= 1;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void k_gemm_nt_h(int M, int N, int K, float alpha,
-                                                   const float *__restrict__ A, int lda,
-                                                   const float *__restrict__ B, int ldb, float beta,
-                                                   float *__restrict__ C, int ldc, int kchunk,
-                                                   float *__restrict__ P, float sa, float sb, int xcd,
-                                                   unsigned *__restrict__ sat) {
-  __shared__ __attribute__((aligned(16))) _Float16 S[2 * 4 * 64 * GH_LD];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wm = wv >> 1, wn = wv & 1;
-  // Workgroups go to the 8 XCDs round-robin in launch order, each XCD with its own 4 MB L2.  With the
-  // plain (x, y, z) order every XCD sees tiles of every k-chunk, i.e. streams BOTH operands whole
-  // (5 + 6 MB for an extrusion round) through its L2; remapped, XCD q owns a contiguous range of the
-  // z-major order -- about one k-chunk, 1.6 MB of operands.  Worth 2.5 % of a reset (45.8 -> 44.6 ms),
-  // no more: the kernel is not bound by where its operands come from (the GEMM notes).
-  int bxi = blockIdx.x, byi = blockIdx.y, bzi = blockIdx.z;
-  if (xcd) {
-    const int T = gridDim.x * gridDim.y * gridDim.z;
-    const int L = bxi + gridDim.x * (byi + gridDim.y * bzi);
-    const int q = L & 7, i = L >> 3;
-    const int lg = q * (T >> 3) + min(q, T & 7) + i;
-    const int xy = gridDim.x * gridDim.y;
-    bzi = lg / xy;
-    const int r = lg - bzi * xy;
-    byi = r / gridDim.x; bxi = r - byi * gridDim.x;
-  }
-  const int m0 = byi * 64, n0 = bxi * 64;
-  const int kb = bzi * kchunk, ke = min(K, kb + kchunk);
-  f32x16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; i++) acc[i] = 0.f;
-  float amax = 0.f;
-  gh_mainloop(A, lda, B, ldb, M, N, m0, n0, kb, ke, S, acc, sa, sb, amax);
-  if (amax > 65504.f) atomicAdd(sat, 1u);        // a scaled operand left the fp16 range and was clipped (rare: one atomic per such thread)
-  const int col = n0 + wn * 32 + (lane & 31);
-  const bool split = gridDim.z > 1;
-#pragma unroll
-  for (int r = 0; r < 16; r++) {
-    int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    if (row < M && col < N) {
-      if (split) {
-        P[((long long)bzi * M + row) * N + col] = acc[r];
-      } else {
-        float *c = C + (long long)row * ldc + col;
-        float v = alpha * acc[r];
-        if (beta != 0.f) v += beta * (*c);
-        *c = v;
-      }
-    }
-  }
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// General batched GEMM for the SAC networks' forward AND backward passes:
-//     C[b] = act( opA(A[b]) . opB(B[b]) + bias[b] ) (+ C[b] when accumulate)
-// opA(A) is M x K, opB(B) is K x N.  TA = false: A stored [M][K] (K contiguous); TA = true: A stored
-// [K][M].  TB = false: B stored [N][K] (the "NT" form above); TB = true: B stored [K][N].
-// The three products of a linear layer y = x W (W stored [in][out]) are
-//     forward  y  = x . W        TA = 0, TB = 1        backward dx = dy . W^T     TA = 0, TB = 0
-//     weights  dW = x^T . dy     TA = 1, TB = 1
-// 64 x 64 tile, LDS rows of 36 floats, one 32x32x2 accumulator per wave; a k-strided operand is read with 128-bit loads
-// along its contiguous (row) direction and transposed on the way into LDS.
-// ---------------------------------------------------------------------------------------------
-template <bool T>
-__device__ __forceinline__ void gg_load(const float *__restrict__ P, int ld, int rows, int r0, int k0,
-                                        int ke, int tid, float (&v)[8], bool vec) {
-  // this thread's 8 elements of the 64 (rows) x 32 (k) tile starting at (r0, k0)
-  if (!T) {
-    const int lr = tid >> 3, lc = (tid & 7) * 4;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const int r = min(r0 + lr + 32 * h, rows - 1);
-      const float *p = P + (long long)r * ld;
-      const int k = k0 + lc;
-      if (k + 3 < ke && vec) {
-        const float4 t = *reinterpret_cast<const float4 *>(p + k);
-        v[4 * h] = t.x; v[4 * h + 1] = t.y; v[4 * h + 2] = t.z; v[4 * h + 3] = t.w;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++) v[4 * h + j] = (k + j < ke) ? p[k + j] : 0.f;
-      }
-    }
-  } else {
-    const int kk = tid >> 4, r4 = (tid & 15) * 4;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const int k = k0 + kk + 16 * h;
-      const float *p = P + (long long)k * ld;
-      if (k < ke) {
-        if (r0 + r4 + 3 < rows && vec) {
-          const float4 t = *reinterpret_cast<const float4 *>(p + r0 + r4);
-          v[4 * h] = t.x; v[4 * h + 1] = t.y; v[4 * h + 2] = t.z; v[4 * h + 3] = t.w;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; j++) v[4 * h + j] = p[min(r0 + r4 + j, rows - 1)];
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++) v[4 * h + j] = 0.f;
-      }
-    }
-  }
-}
-
-template <bool T>
-__device__ __forceinline__ void gg_store(float *S, int tid, const float (&v)[8]) {
-  if (!T) {
-    const int lr = tid >> 3, lc = (tid & 7) * 4;
-#pragma unroll
-    for (int h = 0; h < 2; h++)
-      *reinterpret_cast<float4 *>(S + (lr + 32 * h) * G2_LD + lc) = make_float4(v[4 * h], v[4 * h + 1], v[4 * h + 2], v[4 * h + 3]);
-  } else {
-    const int kk = tid >> 4, r4 = (tid & 15) * 4;
-#pragma unroll
-    for (int h = 0; h < 2; h++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) S[(r4 + j) * G2_LD + kk + 16 * h] = v[4 * h + j];
-  }
-}
-
-// G k-groups of 4 waves share one 64 x 64 output tile: group g runs the K slabs g, g + G, ... through
-// its own double-buffered LDS stage, so G slabs are in flight per block (these products are small --
-// 224 tiles for the SAC layers -- and with one wave per SIMD every slab paid the full L2 / MALL
-// latency); the partial tiles are summed through LDS in a fixed order.
-template <bool TA, bool TB, int G>
-__global__ __launch_bounds__(256 * G) void k_gemm_batched_gen(int M, int N, int K,
-                                                              const float *__restrict__ A, int lda, long long sA,
-                                                              const float *__restrict__ B, int ldb, long long sB,
-                                                              const float *__restrict__ bias, long long sBias,
-                                                              float *__restrict__ C, int ldc, long long sC,
-                                                              int relu, int accumulate, int vecA, int vecB,
-                                                              const float *__restrict__ mask, int ldm, long long sM,
-                                                              int tn, int tm, int ntile) {
-  // mask (the layer's forward output, for the ReLU backward): C = acc where mask > 0, else 0
-  extern __shared__ __attribute__((aligned(16))) float gsm[];
-  // XCD-aware tile order: workgroups go round-robin over the 8 XCDs (each with its own L2), so
-  // workgroup L runs tile (L % 8) * per + L / 8: the tiles of one matrix -- which share A rows and
-  // B columns -- land on one XCD and fetch them into its L2 once instead of once per XCD.
-  const int per = gridDim.x >> 3;
-  const int w = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-  if (w >= ntile) return;
-  const int bz = w / (tn * tm), wt = w - bz * (tn * tm);
-  const int grp = threadIdx.x >> 8, tid = threadIdx.x & 255;
-  float *As = gsm + grp * (4 * 64 * G2_LD), *Bs = As + 2 * 64 * G2_LD;
-  const int lane = tid & 63, wv = tid >> 6, wm = wv >> 1, wn = wv & 1;
-  const int m0 = (wt / tn) * 64, n0 = (wt % tn) * 64;
-  A += (long long)bz * sA; B += (long long)bz * sB; C += (long long)bz * sC;
-  f32x16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; i++) acc[i] = 0.f;
-  const int nslab = (K + 31) / 32, nloop = (nslab + G - 1) / G;      // block-uniform trip count
-  float va[8], vb[8];
-  if (grp < nslab) {
-    gg_load<TA>(A, lda, M, m0, grp * 32, K, tid, va, vecA);
-    gg_load<TB>(B, ldb, N, n0, grp * 32, K, tid, vb, vecB);
-    gg_store<TA>(As, tid, va);
-    gg_store<TB>(Bs, tid, vb);
-  }
-  __syncthreads();
-  const int ro = (lane & 31) * G2_LD + 16 * (lane >> 5);
-  int buf = 0;
-  for (int it = 0; it < nloop; it++, buf ^= 1) {
-    const int slab = it * G + grp;
-    const bool live = slab < nslab, more = slab + G < nslab;
-    if (more) {
-      gg_load<TA>(A, lda, M, m0, (slab + G) * 32, K, tid, va, vecA);
-      gg_load<TB>(B, ldb, N, n0, (slab + G) * 32, K, tid, vb, vecB);
-    }
-    if (live) {
-      const float *as = As + buf * 64 * G2_LD + wm * 32 * G2_LD + ro;
-      const float *bs = Bs + buf * 64 * G2_LD + wn * 32 * G2_LD + ro;
-      float4 a4[4], b4[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        a4[j] = *reinterpret_cast<const float4 *>(as + 4 * j);
-        b4[j] = *reinterpret_cast<const float4 *>(bs + 4 * j);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[j].x, b4[j].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[j].y, b4[j].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[j].z, b4[j].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[j].w, b4[j].w, acc, 0, 0, 0);
-      }
-    }
-    if (more) {
-      gg_store<TA>(As + (buf ^ 1) * 64 * G2_LD, tid, va);
-      gg_store<TB>(Bs + (buf ^ 1) * 64 * G2_LD, tid, vb);
-    }
-    __syncthreads();
-  }
-  if (G > 1) {
-    // partial tiles of groups 1 .. G-1 -> LDS [g-1][r][256 threads]; group 0 adds them in order
-    if (grp > 0) {
-      float *red = gsm + (grp - 1) * (16 * 256);
-#pragma unroll
-      for (int r = 0; r < 16; r++) red[r * 256 + tid] = acc[r];
-    }
-    __syncthreads();
-    if (grp > 0) return;
-#pragma unroll
-    for (int g = 1; g < G; g++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[r] += gsm[(g - 1) * (16 * 256) + r * 256 + tid];
-  }
-  const int col = n0 + wn * 32 + (lane & 31);
-  const float bv = (bias && col < N) ? bias[(long long)bz * sBias + col] : 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; r++) {
-    int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    if (row < M && col < N) {
-      float *c = C + (long long)row * ldc + col;
-      float v = acc[r] + bv;
-      if (accumulate) v += *c;
-      if (relu) v = fmaxf(v, 0.f);
-      if (mask && !(mask[(long long)bz * sM + (long long)row * ldm + col] > 0.f)) v = 0.f;
-      *c = v;
-    }
-  }
-}
-
-__global__ void k_gemm_reduce(int M, int N, int nsplit, float alpha, const float *__restrict__ P,
-                              float beta, float *__restrict__ C, int ldc) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)M * N) return;
-  const int row = (int)(i / N), col = (int)(i - (long long)row * N);
-  const float s = slab_sum<4>(nsplit, [&](int z) { return P[(long long)z * M * N + i]; });
-  float *c = C + (long long)row * ldc + col;
-  float v = alpha * s;
-  if (beta != 0.f) v += beta * (*c);
-  *c = v;
-}
-
-// split-K reduce with the consumer's element-wise step folded in (saves that launch):
-//   mode 1: C = err, com += gain * err                                (Rtc.do_control)
-//   mode 2: C = modes, modes[m] += action[j] * freedom[m] for the action modes  (rl_control)
-struct GemmEpi {
-  int mode;
-  float *com; int ldcom; float gain;
-  const float *gain_row;               // mode 1: per-row (per-environment) integrator gains, or null
-  const float *action; int nact; const int32_t *amode_inv; const float *freedom;
-};
-
-__global__ void k_gemm_reduce_epi(int M, int N, int nsplit, float alpha, const float *__restrict__ P,
-                                  float beta, float *__restrict__ C, int ldc, GemmEpi ep) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)M * N) return;
-  const int row = (int)(i / N), col = (int)(i - (long long)row * N);
-  const float s = slab_sum<4>(nsplit, [&](int z) { return P[(long long)z * M * N + i]; });
-  float *c = C + (long long)row * ldc + col;
-  float v = alpha * s;
-  if (beta != 0.f) v += beta * (*c);
-  if (ep.mode == 1) {
-    ep.com[(long long)row * ep.ldcom + col] += (ep.gain_row ? ep.gain_row[row] : ep.gain) * v;
-  } else if (ep.mode == 2) {
-    const int j = ep.amode_inv[col];
-    if (j >= 0) v += ep.action[(long long)row * ep.nact + j] * ep.freedom[col];
-  }
-  *c = v;
-}
-
-static int g_gemm_target_blocks = 0;     // 0: split-K by the blocks-per-CU cost model (launch_gemm_nt); > 0: about that many blocks
-// power-of-two scale that brings the largest magnitude of a matrix to ~4096 (f16: 11 bits, max 65504)
-static float gemm_scale(const float *h, size_t n) {
-  float m = 0.f;
-  for (size_t i = 0; i < n; i++) m = std::max(m, fabsf(h[i]));
-  if (!(m > 0.f) || !std::isfinite(m)) return 1.f;
-  int e = (int)floorf(log2f(4096.f / m));
-  e = std::max(-10, std::min(24, e));
-  return ldexpf(1.f, e);
-}
 // Arithmetic of the library.  The reference computes in fp32 throughout (Rtc_FFF, shesha/sutra_wrap.py:49; every
 // array cast to np.float32, shesha/init/wfs_init.py:76-101), and so does the DEFAULT here: fp32 operands on fp32
 // matrix instructions (v_mfma_f32_*_f32), fp32 vector arithmetic.  "precision" = 1 (aomarl_set_precision) is the
 // opt-in fast mode: split-fp16 operand pairs (hi + lo, 22-bit mantissa, fp32 accumulation) in the three kernel
 // families that have such a form -- the frame kernel's DFTs, the internal GEMMs, the denoiser.
-static bool g_gemm_split_f16 = false; // "gemm_split_f16": the internal GEMMs (extrusion, command matrix, Btt projections) on k_gemm_nt_h
 int g_precision = 0;                  // process-wide default of every family (aomarl_set_precision)
 // launches per arithmetic family since aomarl_arith_reset (bench.py builds its `dtype` from them)
 // (the AR_* enumeration: aomarl_host.h)
@@ -525,183 +52,8 @@ unsigned long long g_arith[AR_N] = {0, 0, 0, 0, 0, 0, 0};
 static const char *const g_arith_name[AR_N] = {
     "frame_kernel_dft:f32_mfma", "frame_kernel_dft:split_f16_mfma", "gemm:f32_mfma", "gemm:split_f16_mfma",
     "denoiser:f32_mfma", "denoiser:split_f16_mfma", "actor:f32_mfma"};
-static int g_gemm_xcd = 1;            // "gemm_xcd_map": k_gemm_nt_h's / k_gemm_p's blocks grouped by k-chunk per XCD
-static int g_gemm_kgroups = 0;       // batched general GEMM: 0 = by heuristic; 1 / 2 / 4 forced
-// Retired after their A/B runs (profiles/r01g_*): the un-pipelined aligned kernel (30 us vs 22 us per
-// call) and an in-kernel split-K reduction through ticket counters (4x slower: every block pays an
-// L2 write-back for its __threadfence).  k_gemm_nt / k_gemm_nt_batched stay as the fallback
-// for operands that are not 16-byte aligned.
 
-// Threads of k_gemm_nt_h launches that staged an operand beyond the fp16 range (clipped to +-65504): one
-// counter per device, read and cleared by aomarl_gemm_saturated.  The internal call sites scale their
-// operands with margins of 10^2 .. 10^4 over what a closed loop produces (stencil differences x 2^8 up to
-// 255 um, modes x 2^4 up to 4094, slopes x 1); a diverging policy or a runaway loop can leave them.
-static unsigned *g_gemm_sat[64] = {nullptr};
-static unsigned *gemm_sat_counter() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  if (!g_gemm_sat[dev]) {
-    void *p = nullptr;
-    if (hipMalloc(&p, sizeof(unsigned)) != hipSuccess || hipMemset(p, 0, sizeof(unsigned)) != hipSuccess) return nullptr;
-    g_gemm_sat[dev] = (unsigned *)p;
-  }
-  return g_gemm_sat[dev];
-}
-
-// ws / ws_floats: optional split-K workspace (NULL: never split)
-// epi: applied by the split-K reduce when there is one (returns true), else left to the caller
-//      (returns false).  nsplit_out: when non-null and the GEMM was split, NO reduce is launched and
-//      the caller's next kernel sums the partial tiles ws[z][M][N] itself (*nsplit_out = count,
-//      0 = C is final).
-// fast: the split-f16 kernel may be used (internal call sites whose operands are inside its range)
-// force (aomarl_gemm_nt_probe, tests only; null everywhere else): the kernel, tile, k split and block numbering to
-//      take instead of the library's own, and a report of what was launched.  A forced value that cannot be had
-//      is refused (force->error names the argument, nothing is launched), never replaced.
-struct GemmForce {
-  int kernel;            // 0 = the library's choice, 1 = k_gemm_p, 2 = k_gemm_nt (also on aligned operands), 3 = k_gemm_nt_h
-  int wm, wn;            // k_gemm_p's tile (both or neither)
-  int ksplit;            // k-chunks asked for
-  int xcd;               // 0 = the "gemm_xcd_map" option, 1 = on, 2 = off
-  const char *error;     // out: null, or what was refused
-  int r_kernel, r_wm, r_wn, r_nz, r_kchunk;       // out: what was launched
-  GemmPCfg pick;         // out: gemm_p_pick for this shape and workspace, computed afresh beside the memo (wm == 0: k_gemm_p not considered)
-};
-bool launch_gemm_nt(int M, int N, int K, float alpha, const float *A, int lda, const float *B,
-                    int ldb, float beta, float *C, int ldc, hipStream_t s, float *ws = nullptr,
-                    size_t ws_floats = 0, const GemmEpi *epi = nullptr, int *nsplit_out = nullptr,
-                    bool fast = false, float sa = 1.f, float sb = 1.f, float *alpha_out = nullptr,
-                    int min_chunk = 128, int pick_M = 0, GemmForce *force = nullptr) {
-  // alpha_out: the factor the caller must apply to the partial tiles when it sums them itself
-  // pick_M > 0: tile and split-K as a product of pick_M rows would get them (a sum's order depends on the k split
-  //             alone: M rows at once then give, bit for bit, what M / pick_M products of pick_M rows give)
-  if (nsplit_out) *nsplit_out = 0;
-  if (alpha_out) *alpha_out = alpha;
-  if (M <= 0 || N <= 0 || K <= 0) return false;  // (an empty sum: the entry points refuse K == 0, no internal product has one)
-  const int Mp = pick_M > 0 ? pick_M : M;
-  const size_t wsp = pick_M > 0 ? (size_t)((double)ws_floats * Mp / M) : ws_floats;     // the part's share of the workspace
-  const int bx = (N + 63) / 64, by = (M + 63) / 64, byp = (Mp + 63) / 64;
-  int nsplit = 1;
-  bool al = (lda % 4 == 0) && (ldb % 4 == 0) && (((uintptr_t)A & 15) == 0) &&
-            (((uintptr_t)B & 15) == 0);
-  if (force) {
-    force->error = nullptr;
-    force->r_kernel = force->r_wm = force->r_wn = force->r_nz = force->r_kchunk = 0;
-    force->pick = GemmPCfg{0, 0, 0, 0, 0, 0};
-    if ((force->kernel == 1 || force->kernel == 3 || force->wm || force->wn) && !al) { force->error = "kernel / wm / wn (operands not 16-byte aligned)"; return false; }
-    if ((force->wm || force->wn) && !gemm_p_on_menu(force->wm, force->wn)) { force->error = "wm / wn (not an instantiated tile)"; return false; }
-    if ((force->wm || force->wn) && force->kernel != 0 && force->kernel != 1) { force->error = "wm / wn (k_gemm_p only)"; return false; }
-    if (force->ksplit < 0 || (force->ksplit > 1 && !ws)) { force->error = "ksplit (no workspace)"; return false; }
-    if (force->kernel == 2) al = false;          // the element-wise kernel on aligned operands
-  }
-  const int xcd = force && force->xcd ? (force->xcd == 1 ? 1 : 0) : g_gemm_xcd;
-  if (ws && bx * byp < 384) {
-    // Split K so that the launch is as short as its slowest CU: blocks go round-robin over the 256 CUs, a CU
-    // that gets one block more than the others sets the duration (528 blocks = 2.06 per CU took as long as 768
-    // would: 132 tiles x 4 chunks lost to 132 x 3 = 396).  Cost model per candidate: blocks per CU (rounded
-    // up) x k-tiles per block (whole groups of three for the pipelined kernels, + 2 tiles of fill / drain).
-    // min_chunk: the control chain's products ask for at least three groups of three k-tiles per block
-    // (288): below that the fill / drain of the load pipeline and the wider reduce cost more than the
-    // extra blocks bring (round-2 script gemm_split_time.py, since removed).
-    const int ncu = 256, tiles = bx * byp;
-    if (g_gemm_target_blocks > 0) {              // "gemm_target_blocks" > 0: the plain rule (about that many blocks)
-      nsplit = (g_gemm_target_blocks + tiles - 1) / tiles;
-      if (nsplit > 8) nsplit = 8;
-      while (nsplit > 1 && (K / nsplit < min_chunk || (size_t)nsplit * Mp * N > wsp)) nsplit--;
-    } else {
-      long long best = -1;
-      for (int ns = 1; ns <= 8; ns++) {
-        if (ns > 1 && (K / ns < min_chunk || (size_t)ns * Mp * N > wsp)) break;
-        const int chunk = al ? ((K + ns - 1) / ns + 95) / 96 * 96 : (((K + ns - 1) / ns + 31) & ~31);
-        const int nz = (K + chunk - 1) / chunk;
-        const long long per_cu = ((long long)tiles * nz + ncu - 1) / ncu;
-        const long long cost = per_cu * (chunk / 32 + 3);
-        if (best < 0 || cost < best) { best = cost; nsplit = ns; }
-      }
-    }
-  }
-  const bool split_f16 = al && ((fast && g_gemm_split_f16) || (force && force->kernel == 3));
-  if (al && !split_f16) {
-    // round 4: the balanced kernel; tile and k split from its own cost model (memoised per shape)
-    struct Memo { int M, N, K; size_t ws; GemmPCfg c; };
-    static thread_local Memo memo[16];
-    static thread_local int memo_n = 0;
-    const size_t wsf = ws ? wsp : 0;
-    const GemmPCfg *cfg = nullptr;
-    GemmPCfg fresh;
-    if (force) {                                 // a probe call reports the pick computed afresh
-      force->pick = fresh = gemm_p_pick(Mp, N, K, wsf, ws ? 16 : 1);
-      if (force->wm || force->ksplit) cfg = &fresh;          // forced: the memo is neither read nor written
-    }
-    for (int i = 0; i < memo_n && !cfg; i++)
-      if (memo[i].M == Mp && memo[i].N == N && memo[i].K == K && memo[i].ws == wsf) { cfg = &memo[i].c; break; }
-    if (!cfg) {
-      Memo &m = memo[memo_n < 16 ? memo_n++ : (memo_n = 1, 0)];
-      m.M = Mp; m.N = N; m.K = K; m.ws = wsf;
-      m.c = gemm_p_pick(Mp, N, K, wsf, ws ? 16 : 1);
-      cfg = &m.c;
-    }
-    GemmPCfg mine = *cfg;                        // (pick_M: the part's tile and k split over this product's rows)
-    if (force && (force->wm || force->ksplit)) {   // forced tile and / or k split: the other one stays the pick's
-      gemm_p_cost(Mp, N, K, force->wm ? force->wm : mine.wm, force->wm ? force->wn : mine.wn,
-                  force->ksplit ? force->ksplit : mine.nz, &mine);
-      if (mine.nz > 1 && (size_t)mine.nz * M * N > ws_floats) { force->error = "ksplit (the slabs do not fit work_floats)"; return false; }
-    }
-    if (mine.wm > 0) mine.tiles_m = (M + 32 * mine.wm - 1) / (32 * mine.wm);
-    cfg = &mine;
-    if (cfg->wm > 0 && gemm_p_launch(*cfg, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, ws, xcd, s)) {
-      g_arith[AR_GEMM_F32]++;
-      nsplit = cfg->nz;
-      if (force) { force->r_kernel = 1; force->r_wm = cfg->wm; force->r_wn = cfg->wn; force->r_nz = cfg->nz; force->r_kchunk = cfg->kchunk; }
-      if (nsplit > 1) {
-        const long long tot = (long long)M * N;
-        if (nsplit_out) { *nsplit_out = nsplit; return false; }
-        if (epi) {
-          hipLaunchKernelGGL(k_gemm_reduce_epi, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, M, N,
-                             nsplit, alpha, ws, beta, C, ldc, *epi);
-          return true;
-        }
-        hipLaunchKernelGGL(k_gemm_reduce, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, M, N,
-                           nsplit, alpha, ws, beta, C, ldc);
-      }
-      return false;
-    }
-    if (force && (force->kernel == 1 || force->wm)) { force->error = "kernel (k_gemm_p could not be launched)"; return false; }
-  }
-  if (force && force->ksplit) nsplit = force->ksplit;
-  int kchunk = ((K + nsplit - 1) / nsplit + 31) & ~31;
-  if (al)                                        // whole groups of three k-tiles (g3_mainloop / gh_mainloop)
-    kchunk = ((K + nsplit - 1) / nsplit + 95) / 96 * 96;
-  nsplit = (K + kchunk - 1) / kchunk;
-  if (force && force->ksplit && nsplit > 1 && (size_t)nsplit * M * N > ws_floats) { force->error = "ksplit (the slabs do not fit work_floats)"; return false; }
-  dim3 grid(bx, by, nsplit);
-  unsigned *sat = split_f16 ? gemm_sat_counter() : nullptr;
-  if (force && force->kernel == 3 && !sat) { force->error = "kernel (no saturation counter for k_gemm_nt_h)"; return false; }
-  if (force) { force->r_kernel = split_f16 && sat ? 3 : 2; force->r_wm = force->r_wn = 2; force->r_nz = nsplit; force->r_kchunk = kchunk; }
-  if (split_f16 && sat) {
-    alpha /= (sa * sb);                            // also what the split-K reduce below applies
-    if (alpha_out) *alpha_out = alpha;
-    hipLaunchKernelGGL(k_gemm_nt_h, grid, dim3(256), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, C,
-                       ldc, kchunk, ws, sa, sb, xcd, sat);
-    g_arith[AR_GEMM_SPLIT]++;
-  }
-  else {
-    hipLaunchKernelGGL(k_gemm_nt, grid, dim3(256), 0, s, M, N, K, alpha, A, lda, B, ldb,
-                       beta, C, ldc, kchunk, ws);
-    g_arith[AR_GEMM_F32]++;
-  }
-  if (nsplit > 1) {
-    const long long tot = (long long)M * N;
-    if (nsplit_out) { *nsplit_out = nsplit; return false; }
-    if (epi) {
-      hipLaunchKernelGGL(k_gemm_reduce_epi, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, M, N,
-                         nsplit, alpha, ws, beta, C, ldc, *epi);
-      return true;
-    }
-    hipLaunchKernelGGL(k_gemm_reduce, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, M, N,
-                       nsplit, alpha, ws, beta, C, ldc);
-  }
-  return false;
-}
+#include "aomarl_gemm_nt.h"           // the loop's products: k_gemm_nt, k_gemm_nt_h, k_gemm_batched_gen, launch_gemm_nt
 
 // =============================================================================================
 // atmosphere: Fried-Clark extrusion on ring-buffered screens

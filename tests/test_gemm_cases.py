@@ -144,11 +144,21 @@ def test_probe_structs_match_the_header():
 
 
 def test_gemm_p_host_check_program(tmp_path):
-    """aomarl_gemm_p_host.h through its stand-alone program: every configuration gemm_p_pick returns over the grid of
-    shapes, K = 1 .. 4100, with and without a workspace, is one k_gemm_p can run (see the program's header)."""
+    """aomarl_gemm_p_host.h and aomarl_gemm_plan_host.h through their stand-alone program: every configuration
+    gemm_p_pick returns over the grid of shapes, K = 1 .. 4100, with and without a workspace, is one k_gemm_p can run,
+    and every plan launch_gemm_nt makes over that grid x alignment x options is one its kernels and reduces can run
+    (see the program's header).  The plans of the loop's own shapes are the pinned ones (tests/golden/gemm_plans.txt,
+    recorded from the launcher before it had a plan)."""
     exe = str(tmp_path / "gemm_p_host_check")
     subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-o", exe,
                            os.path.join(CSRC, "gemm_p_host_check.cpp")])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode == 0, r.stderr.decode()
-    assert r.stdout.decode().startswith("gemm_p_host_check: ok (3968800 configurations")
+    lines = r.stdout.decode().splitlines()
+    assert len(lines) == 2
+    assert lines[0].startswith("gemm_p_host_check: ok (3968800 configurations")
+    assert lines[1].startswith("gemm_plan: ok (388876800 plans")
+    r = subprocess.run([exe, "--plans"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=60)
+    assert r.returncode == 0, r.stderr.decode()
+    want = open(os.path.join(ROOT, "tests", "golden", "gemm_plans.txt")).read()
+    assert len(want.splitlines()) == 960 and r.stdout.decode() == want
