@@ -139,6 +139,11 @@ struct aomarl_ctx {
   int32_t *amodes = nullptr, *amode_inv = nullptr;   // action modes and their inverse map [nmodes]
   float *env_gain = nullptr;       // per-environment integrator gains (aomarl_set_env_gains) or null
   int env_gain_n = 0;
+  // per-mode gain factors in Btt coordinates (aomarl_set_modal_gains) or null: device [mgain_rows][mgain_nm], rows = 1
+  // (shared) or one per environment; h_mgain: the host copy aomarl_get_modal_gains hands back
+  float *mgain = nullptr;
+  int mgain_rows = 0, mgain_nm = 0;
+  std::vector<float> h_mgain;
   uint32_t *seed_stage = nullptr;  // device staging for reset seeds
   int seed_stage_n = 0;
   // aomarl_reset_prefetch_*: the NEXT episode's screens grown in a shadow state while this episode runs
@@ -692,6 +697,7 @@ int aomarl_destroy(aomarl_ctx *c) {
   if (c->ev_moved) (void)hipEventDestroy(c->ev_moved);
   if (c->ev_psf) (void)hipEventDestroy(c->ev_psf);
   if (c->env_gain) (void)hipFree(c->env_gain);
+  if (c->mgain) (void)hipFree(c->mgain);
   if (c->seed_stage) (void)hipFree(c->seed_stage);
   rp_free(c);
   if (c->timg) (void)hipFree(c->timg);
@@ -760,6 +766,55 @@ int aomarl_set_env_gains(aomarl_ctx *c, const float *gains, int nenv) {
     c->env_gain_n = nenv;
   }
   HIPCHK(hipMemcpy(c->env_gain, gains, sizeof(float) * (size_t)nenv, hipMemcpyHostToDevice));
+  return 0;
+}
+
+int aomarl_set_modal_gains(aomarl_ctx *c, const float *mgain, int nrows, int nmodes) {
+  if (c) c->cfg_epoch++;
+  if (!c) return fail("set_modal_gains: null ctx");
+  if (c->pipe.active)
+    return fail("aomarl_set_modal_gains: a pipelined frame is in flight (aomarl_set_frame_pipeline): the frame pipeline "
+                "cannot apply or drop modal gains within an episode -- reset first");
+  if (!mgain) {                      // back to the scalar law
+    if (c->mgain) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(c->mgain); }
+    c->mgain = nullptr; c->mgain_rows = 0; c->mgain_nm = 0; c->h_mgain.clear();
+    return 0;
+  }
+  if (!c->v2m || !c->m2v) return fail("set_modal_gains: no modal basis (aomarl_set_modal)");
+  if (nmodes != c->nmodes) return fail("set_modal_gains: nmodes = %d, the modal basis has %d modes", nmodes, c->nmodes);
+  if (nrows < 1) return fail("set_modal_gains: nrows = %d: 1 (shared) or one row per environment", nrows);
+  const size_t cnt = (size_t)nrows * (size_t)nmodes;
+  for (size_t i = 0; i < cnt; i++)
+    if (!(mgain[i] >= 0.f) || !isfinite(mgain[i]))
+      return fail("set_modal_gains: mgain[%zu][%zu] = %g: entries must be finite and not negative", i / nmodes, i % nmodes, (double)mgain[i]);
+  if ((size_t)c->mgain_rows * (size_t)c->mgain_nm != cnt) {
+    if (c->mgain) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(c->mgain); c->mgain = nullptr; c->mgain_rows = 0; c->mgain_nm = 0; c->h_mgain.clear(); }
+    HIPCHK(hipMalloc((void **)&c->mgain, sizeof(float) * cnt));
+  } else {
+    HIPCHK(hipDeviceSynchronize());   // a kernel in flight may still read the old values
+  }
+  c->mgain_rows = nrows; c->mgain_nm = nmodes;
+  c->h_mgain.assign(mgain, mgain + cnt);
+  HIPCHK(hipMemcpy(c->mgain, mgain, sizeof(float) * cnt, hipMemcpyHostToDevice));
+  return 0;
+}
+
+int aomarl_get_modal_gains(aomarl_ctx *c, float *mgain_out, int *nrows_out, int *nmodes_out) {
+  if (!c) return fail("get_modal_gains: null ctx");
+  if (nrows_out) *nrows_out = c->mgain ? c->mgain_rows : 0;
+  if (nmodes_out) *nmodes_out = c->mgain ? c->mgain_nm : 0;
+  if (mgain_out && c->mgain) memcpy(mgain_out, c->h_mgain.data(), sizeof(float) * c->h_mgain.size());
+  return 0;
+}
+
+// modal gains are set: do they fit this basis and this state?  (name: the entry point asking)
+static int mgain_check(const aomarl_ctx *c, int nenv, const char *name) {
+  if (c->mgain_nm != c->nmodes)
+    return fail("%s: modal gains were set for %d modes, the basis now has %d (aomarl_set_modal_gains again, or clear them)",
+                name, c->mgain_nm, c->nmodes);
+  if (c->mgain_rows != 1 && c->mgain_rows != nenv)
+    return fail("%s: aomarl_set_modal_gains was given nrows = %d, the state has %d environments (1 or %d rows)", name,
+                c->mgain_rows, nenv, nenv);
   return 0;
 }
 

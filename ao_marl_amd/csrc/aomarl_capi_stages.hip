@@ -228,11 +228,61 @@ int aomarl_slopes_geom(aomarl_ctx *c, aomarl_state *st, int b, int n, void *stre
 }
 
 // ---------------------------------------------------------------- controller
+// modal gains (aomarl_set_modal_gains): the residual modes of rows [b, b + n), scaled in place by
+// (gain or that environment's gain) * mgain[row or 0][m]
+__global__ void k_mgain_scale(float *__restrict__ modes, int ldm, int nm, float gain, const float *__restrict__ env_gain,
+                              const float *__restrict__ mgain, int mg_rows, int env_begin) {
+  const int r = blockIdx.y, m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= nm) return;
+  const int e = env_begin + r;
+  const float g = env_gain ? env_gain[e] : gain;
+  modes[(long long)r * ldm + m] *= g * mgain[(long long)(mg_rows > 1 ? e : 0) * nm + m];
+}
+
+// do_control under modal gains: err as ever (no integration in actuator space), then
+// com += m2v . (gain * mgain (.) e),  e = -s2m . slopes
+static int do_control_modal(aomarl_ctx *c, aomarl_state *st, int b, int n, void *stream) {
+  int rc = mgain_check(c, st->nenv, "do_control");
+  if (rc) return rc;
+  if (!c->v2m || !c->m2v) return fail("do_control: modal gains are set (aomarl_set_modal_gains) but no modal basis (aomarl_set_modal)");
+  if (!c->s2m || c->s2m_nmodes != c->nmodes)
+    return fail("do_control: modal gains are set (aomarl_set_modal_gains): the integrator runs in Btt coordinates and needs "
+                "the slopes-to-modes matrix of these %d modes (aomarl_set_slopes2modes)", c->nmodes);
+  if (c->env_gain && c->env_gain_n != st->nenv)
+    return fail("do_control: %d per-environment gains set, the state has %d environments", c->env_gain_n, st->nenv);
+  hipStream_t s = (hipStream_t)stream;
+  const int na = c->sys.nactu, nsl = c->sys.nslope, nm = c->nmodes;
+  Work w = work_layout(c, st->nenv);
+  const float *slopes = st->slopes + (size_t)b * nsl;
+  GemmArgs ge(n, na, nsl, -1.0f, slopes, nsl, c->cmat, c->ld_cmat, 0.0f, st->err + (size_t)b * st->ld_actu, st->ld_actu, s);
+  ge.ws = st->work + w.GEMM; ge.ws_floats = w.gemm_floats; ge.min_chunk = 288;
+  ge.fast = true; ge.sb = c->cmat_scale;
+  launch_gemm_nt(ge);
+  LAUNCHCHK();
+  float *modes = st->work + w.MODES + (size_t)b * w.ldm;
+  GemmArgs gs(n, nm, nsl, -1.0f, slopes, nsl, c->s2m, c->ld_cmat, 0.0f, modes, w.ldm, s);
+  gs.ws = st->work + w.GEMM; gs.ws_floats = w.gemm_floats; gs.min_chunk = 288;
+  gs.fast = true; gs.sb = c->s2m_scale;
+  launch_gemm_nt(gs);
+  LAUNCHCHK();
+  hipLaunchKernelGGL(k_mgain_scale, dim3((nm + 255) / 256, n), dim3(256), 0, s, modes, w.ldm, nm, c->gain, c->env_gain,
+                     c->mgain, c->mgain_rows, b);
+  LAUNCHCHK();
+  float *com = st->com + (size_t)b * st->ld_actu;
+  GemmArgs gm(n, na, nm, 1.0f, modes, w.ldm, c->m2v, c->ld_m2v, 1.0f, com, st->ld_actu, s);
+  gm.ws = st->work + w.GEMM; gm.ws_floats = w.gemm_floats; gm.min_chunk = 288;
+  gm.fast = true; gm.sa = 16.f; gm.sb = c->m2v_scale;        /* Btt coordinates x 2^4 */
+  launch_gemm_nt(gm);
+  LAUNCHCHK();
+  return 0;
+}
+
 int aomarl_do_control(aomarl_ctx *c, aomarl_state *st, int b, int n, void *stream) {
   int rc = check_range(c, st, b, n);
   if (rc) return rc;
   if (!c->cmat) return fail("do_control: no command matrix (aomarl_set_cmat)");
   if (n == 0) return 0;
+  if (c->mgain) return do_control_modal(c, st, b, n, stream);
   hipStream_t s = (hipStream_t)stream;
   const int na = c->sys.nactu, nsl = c->sys.nslope;
   // err[env][a] = - sum_s slopes[env][s] cmat[a][s]
@@ -380,6 +430,26 @@ __global__ __launch_bounds__(256) void k_compose_rewards(int nm, const float *__
   if (modes_out) modes_out[(long long)r * nm + m] = v;
 }
 
+// k_modal_compose under modal gains (aomarl_set_modal_gains): modes = m0 + (g * mgain[m]) * m1, in that order -- with
+// mgain = 1 the product g * 1 is g and the rest is k_modal_compose's expression: the same bits
+__global__ void k_modal_compose_mgain(int nm, const float *__restrict__ m0, const float *__restrict__ m1,
+                                      float g, const float *__restrict__ mgain, int mg_rows, int env_begin,
+                                      const float *__restrict__ action, int nact,
+                                      const int32_t *__restrict__ amode_inv,
+                                      const float *__restrict__ freedom, float *__restrict__ modes, int ldm,
+                                      float *__restrict__ modes_out) {
+  const int r = blockIdx.y, m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= nm) return;
+  const float gm = g * mgain[(long long)(mg_rows > 1 ? env_begin + r : 0) * nm + m];
+  float v = m0[(long long)r * nm + m] + gm * m1[(long long)r * nm + m];
+  if (action) {
+    const int j = amode_inv[m];
+    if (j >= 0) v += action[(long long)r * nact + j] * freedom[m];
+  }
+  modes[(long long)r * ldm + m] = v;
+  if (modes_out) modes_out[(long long)r * nm + m] = v;
+}
+
 int aomarl_rl_control_modes(aomarl_ctx *c, aomarl_state *st, int b, int n, const float *m0,
                             const float *m1, float g, const float *action, float *modes_out,
                             void *stream) {
@@ -388,13 +458,18 @@ int aomarl_rl_control_modes(aomarl_ctx *c, aomarl_state *st, int b, int n, const
   if (!c->v2m || !c->m2v) return fail("rl_control_modes: no modal basis (aomarl_set_modal)");
   if (!m0 || !m1) return fail("rl_control_modes: null modal vectors");
   if (action && c->nact <= 0) return fail("rl_control_modes: no action modes set");
+  if (c->mgain && (rc = mgain_check(c, st->nenv, "rl_control_modes"))) return rc;
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   Work w = work_layout(c, st->nenv);
   float *modes = st->work + w.MODES;
   const int na = c->sys.nactu, nm = c->nmodes;
-  hipLaunchKernelGGL(k_modal_compose, dim3((nm + 255) / 256, n), dim3(256), 0, s, nm, m0, m1, g, action,
-                     c->nact, c->amode_inv, c->freedom, modes, w.ldm, modes_out);
+  if (c->mgain)
+    hipLaunchKernelGGL(k_modal_compose_mgain, dim3((nm + 255) / 256, n), dim3(256), 0, s, nm, m0, m1, g, c->mgain,
+                       c->mgain_rows, b, action, c->nact, c->amode_inv, c->freedom, modes, w.ldm, modes_out);
+  else
+    hipLaunchKernelGGL(k_modal_compose, dim3((nm + 255) / 256, n), dim3(256), 0, s, nm, m0, m1, g, action,
+                       c->nact, c->amode_inv, c->freedom, modes, w.ldm, modes_out);
   LAUNCHCHK();
   GemmArgs ga(n, na, nm, 1.0f, modes, w.ldm, c->m2v, c->ld_m2v, 0.0f, st->com + (size_t)b * st->ld_actu, st->ld_actu, s);
   ga.ws = st->work + w.GEMM; ga.ws_floats = w.gemm_floats; ga.min_chunk = 288;

@@ -246,7 +246,7 @@ __global__ __launch_bounds__(256) void k_small_tail(DevState st, SmallTail p, St
 
 static bool small_chain_ok(const aomarl_ctx *c, const aomarl_env_glue *g) {
   return c->small_chain && c->sys.nactu <= SMALL_NA && c->sys.nslope <= SMALL_NSL && g->nmodes <= SMALL_NM &&
-         (long long)c->sys.nactu * c->sys.nslope <= 65536 && c->cmat && !c->env_gain;
+         (long long)c->sys.nactu * c->sys.nslope <= 65536 && c->cmat && !c->env_gain && !c->mgain;
 }
 
 // may the chain run in its fused form?  (ktt: index of the tip-tilt mirror)
@@ -257,7 +257,8 @@ static bool env_step_fusable(aomarl_ctx *c, const aomarl_env_glue *g, int *ktt_o
   }
   const bool defer = c->defer_dm_shape && aomarl_dm_from_voltage_available(c);
   if (ktt_out) *ktt_out = ktt;
-  return !(g->flags & AOMARL_ENV_STEP_UNFUSED) && ntt == 1 && (defer || nother == 0);
+  // (modal gains, aomarl_set_modal_gains: the general chain -- aomarl_rl_control_modes and aomarl_do_control apply them)
+  return !(g->flags & AOMARL_ENV_STEP_UNFUSED) && ntt == 1 && (defer || nother == 0) && !c->mgain;
 }
 
 // ---- AoEnv.rl_step, fused form: Btt correction from the coordinates at hand (+ the per-agent rewards of the
@@ -341,7 +342,7 @@ static int env_step_head_fused(aomarl_ctx *c, aomarl_state *st, aomarl_state *st
 
 // the residual shortcut applies: the matrix is there for these modes and the integrator gain is one scalar
 static bool env_step_shortcut(const aomarl_ctx *c, const aomarl_env_glue *g) {
-  return c->residual_shortcut && c->s2m && c->s2m_nmodes == g->nmodes && !c->env_gain;
+  return c->residual_shortcut && c->s2m && c->s2m_nmodes == g->nmodes && !c->env_gain && !c->mgain;
 }
 
 // ---- the rest of AoEnv.linear_step behind do_control: v2m . err, the state blocks
@@ -514,7 +515,7 @@ static bool pipe_eligible(aomarl_ctx *c, const aomarl_state *st, const aomarl_en
   return P.have_twin && c->pipe_enabled && P.owner_screens == st->screens && !c->graph_step && !c->capturing && c->prefetch_atmos &&
          c->delay == 1.f && c->sys.noise < 0.f && !g->denoiser && accumx && accumy && !c->subpixel_flow &&
          aomarl_frame_fused_available(c) && c->defer_dm_shape && aomarl_dm_from_voltage_available(c) &&
-         env_step_fusable(c, g, nullptr);
+         env_step_fusable(c, g, nullptr) && !c->mgain;
 }
 
 static int pipe_init(aomarl_ctx *c, const aomarl_state *st) {
@@ -759,8 +760,9 @@ int aomarl_env_step(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const f
     return env_step_pipelined(c, st, g, action, gain, accumx, accumy, state_out, reward_out, stream);
   if (c->pipe.active && c->pipe.owner_screens == st->screens)
     return fail("env_step: a pipelined frame is in flight but this call is not eligible for the frame pipeline "
-                "(options, glue or arguments changed within an episode): reset first");
-  if (!c->graph_step || c->capturing) return env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, stream);
+                "(options, glue or arguments changed within an episode, or aomarl_set_modal_gains): reset first");
+  // (modal gains: no replay -- the general chain, launched call by call)
+  if (!c->graph_step || c->capturing || c->mgain) return env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, stream);
   const int n = st->nenv, nl = c->nlayers;
   // the steady state only: a prefetched move of exactly this batch is pending, the glue has been validated by a
   // plain call, every environment moves by the same plan

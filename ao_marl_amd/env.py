@@ -384,6 +384,24 @@ class VecRlSupervisor(object):
             self.sim.set_env_gains(g)
             self.gain, self._env_gains = None, True
 
+    def set_modal_gains(self, mgain):
+        """Per-mode integrator gains in Btt coordinates, a FACTOR on the scalar gain (upstream's modal optimisation,
+        rtc_init.py:506-513): m[t] = m[t-1] + gain * mgain[m] * e[t] with e = -s2m . slopes.  [nmodes] for all
+        environments, [nenv][nmodes] for one vector each, None for the scalar law again.  Every control path applies
+        them (do_control, rl_control_modes, the one-call step, which then runs the general chain; see DESIGN.md);
+        modal_gains.ModalGainOptimizer finds them."""
+        if not hasattr(self.sim, "set_modal_gains"):
+            raise NotImplementedError("set_modal_gains: this simulator backend has no modal gains")
+        if mgain is not None:
+            self.ensure_slopes2modes()          # the integrator runs in Btt coordinates
+        self.sim.set_modal_gains(mgain)
+
+    @property
+    def modal_gains(self):
+        """The modal gains as set ([1 or nenv][nmodes]) or None."""
+        get = getattr(self.sim, "get_modal_gains", None)
+        return get() if get is not None else None
+
     def obtain_and_set_cmat_filtered(self, modes_filtered):
         """Command matrix through the Btt basis without its last `modes_filtered` (non-TT) modes
         (rlSupervisor.py:215-234 -> basis.compute_cmat_with_Btt)."""
@@ -394,6 +412,8 @@ class VecRlSupervisor(object):
         self.s.cmat = np.ascontiguousarray(cmat)
         self.sim.set_cmat(self.s.cmat)
         self._s2m_ok = False
+        if self.modal_gains is not None:        # their integrator needs v2m . cmat of the new matrix
+            self.ensure_slopes2modes()
 
     @property
     def projector_wfs2modes(self):

@@ -87,6 +87,8 @@ SYMBOLS = [
     ("aomarl_set_cmat", _i, [_vp, _fp]),
     ("aomarl_set_gain", _i, [_vp, _f]),
     ("aomarl_set_env_gains", _i, [_vp, _fp, _i]),
+    ("aomarl_set_modal_gains", _i, [_vp, _fp, _i, _i]),
+    ("aomarl_get_modal_gains", _i, [_vp, _fp, C.POINTER(_i), C.POINTER(_i)]),
     ("aomarl_set_modal", _i, [_vp, _i, _fp, _fp, _fp, _i, _ip]),
     ("aomarl_workspace_floats", C.c_size_t, [_vp, _i]),
     ("aomarl_screen_stride", C.c_size_t, [_vp]),
@@ -169,6 +171,11 @@ SYMBOLS = [
     ("aomarl_roket_moments", _i, [_vp, _vp, _vp, C.POINTER(C.c_longlong), _vp]),
     ("aomarl_roket_reset", _i, [_vp]),
     ("aomarl_roket_history", _i, [_vp, _vp, _vp, _vp]),
+    ("aomarl_modopti_create", _i, [_vp, C.POINTER(C.c_void_p)]),
+    ("aomarl_modopti_destroy", _i, [_vp]),
+    ("aomarl_modopti_reset", _i, [_vp]),
+    ("aomarl_modopti_accumulate", _i, [_vp, _vp, _i, C.c_longlong, _vp]),
+    ("aomarl_modopti_result", _i, [_vp, _vp, _vp, _ip, C.POINTER(C.c_longlong), _vp]),
     ("aomarl_psfrec_create", _i, [_vp, C.POINTER(C.c_void_p)]),
     ("aomarl_psfrec_destroy", _i, [_vp]),
     ("aomarl_psfrec_accumulate", _i, [_vp, _vp, _vp, _i, _vp]),
@@ -280,6 +287,11 @@ class RoketDesc(C.Structure):
     """aomarl_roket_desc (include/aomarl.h)"""
     _fields_ = [(n, C.c_int32) for n in ("nenv", "nactu", "ld_actu", "nmodes", "nfiltered", "delay")] + \
                [("g", C.c_float), ("gamma", C.c_float), ("RD", _fp), ("P", _fp), ("Btt", _fp)]
+
+
+class ModoptiDesc(C.Structure):
+    """aomarl_modopti_desc (include/aomarl.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("nenv", "nmodes", "ngain", "nskip")] + [("delay", C.c_float), ("gains", _fp)]
 
 
 class PsfRecDesc(C.Structure):

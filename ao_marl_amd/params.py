@@ -98,7 +98,9 @@ class Param_centroider(_P):
 
 class Param_controller(_P):
     _defaults = dict(type=None, nwfs=None, ndm=None, maxcond=None, delay=None, gain=None,
-                     nmodes=None, modopti=False, do_kl_imat=False, nstates=0)
+                     nmodes=None, modopti=False, do_kl_imat=False, nstates=0,
+                     # modal gain optimisation (PCONTROLLER.py:78-88): frames recorded, the grid of gains
+                     nrec=2048, gmin=0.0, gmax=1.0, ngain=15)
 
 
 class ParamSet(object):

@@ -136,6 +136,9 @@ def _roket_supervisor(env):
     if sup.gain is None or getattr(sup, "_env_gains", False):
         raise RuntimeError("VecRoket: per-environment gains (set_env_gains) are not supported: the loop filter gRD is "
                            "one matrix for all environments")
+    if getattr(sup, "modal_gains", None) is not None:
+        raise RuntimeError("VecRoket: modal gains (set_modal_gains) are not supported: the loop filter gRD assumes the "
+                           "scalar integrator law; clear them with set_modal_gains(None)")
     if sup.geo is None:
         raise RuntimeError("VecRoket: the fitting term and B come from the geometric twin; build the environment "
                            "with geo=True")

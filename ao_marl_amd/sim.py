@@ -320,6 +320,32 @@ class HipSim(object):
             raise ValueError("one gain per environment: expected %d, got %d" % (self.nenv, g.size))
         la.check(self.lib.aomarl_set_env_gains(self.ctx, la.fptr(g), int(g.size)))
 
+    def set_modal_gains(self, mgain):
+        """Per-mode gain factors in Btt coordinates (aomarl_set_modal_gains): [nmodes] for all environments or
+        [nenv][nmodes]; None clears them.  m[t] = m[t-1] + gain * mgain[m] * e[t] in do_control, rl_control_modes and
+        env_step (which then runs the general chain)."""
+        if mgain is None:
+            la.check(self.lib.aomarl_set_modal_gains(self.ctx, None, 0, 0))
+            return
+        g = np.ascontiguousarray(mgain, dtype=np.float32)
+        if g.ndim == 1:
+            g = g[None, :]
+        if g.ndim != 2:
+            raise ValueError("mgain must be [nmodes] or [nenv][nmodes], got shape %s" % (g.shape,))
+        if g.shape[0] not in (1, self.nenv):
+            raise ValueError("mgain: nrows = %d, expected 1 or nenv = %d" % (g.shape[0], self.nenv))
+        la.check(self.lib.aomarl_set_modal_gains(self.ctx, la.fptr(g), int(g.shape[0]), int(g.shape[1])))
+
+    def get_modal_gains(self):
+        """The modal gains as set ([nrows][nmodes] float32), or None (aomarl_get_modal_gains)."""
+        nr, nm = C.c_int(0), C.c_int(0)
+        la.check(self.lib.aomarl_get_modal_gains(self.ctx, None, C.byref(nr), C.byref(nm)))
+        if nr.value == 0:
+            return None
+        out = np.empty((nr.value, nm.value), dtype=np.float32)
+        la.check(self.lib.aomarl_get_modal_gains(self.ctx, la.fptr(out), C.byref(nr), C.byref(nm)))
+        return out
+
     def set_modal(self, v2m, m2v, freedom=None, action_modes=None):
         v2m = np.ascontiguousarray(v2m, dtype=np.float32)
         m2v = np.ascontiguousarray(m2v, dtype=np.float32)

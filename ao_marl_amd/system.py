@@ -89,7 +89,13 @@ def from_system(sysm, ncontrol=0, strehl_halfwin=16):
     # controller
     s.delay = float(ctl.delay)
     s.gain = float(ctl.gain)
-    s.cmat = None   # filled by modal.calibrate()
+    # modal gain optimisation (PCONTROLLER.py:78-88): read here, used by modal_gains.optimize_modal_gains alone
+    s.modopti = bool(getattr(ctl, "modopti", False) or False)
+    s.nrec = int(getattr(ctl, "nrec", None) or 2048)
+    s.gmin = float(getattr(ctl, "gmin", None) or 0.0)
+    s.gmax = float(1.0 if getattr(ctl, "gmax", None) is None else ctl.gmax)
+    s.ngain = int(getattr(ctl, "ngain", None) or 15)
+    s.cmat = None  # filled by modal.calibrate()
     return s
 
 

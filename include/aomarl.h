@@ -176,6 +176,23 @@ int aomarl_set_gain(aomarl_ctx *ctx, float gain); /* d_control[0].set_gain (ao_e
  * ONE batch, environment e running the reference's loop with gain gains[e].  NULL: scalar again.
  * Applies to aomarl_do_control only; the RL control entry points take their gain as an argument. */
 int aomarl_set_env_gains(aomarl_ctx *ctx, const float *gains, int nenv);
+/* Per-mode integrator gains in Btt coordinates (upstream's modal optimisation, rtc_init.py:506-513: com -= gain *
+ * mgain (.) err).  With e = -s2m . slopes (aomarl_slopes2modes) and m = v2m . com the law becomes
+ *     m[t] = m[t-1] + gain * mgain[m] * e[t],   com[t] = m2v . m[t]
+ * mgain: HOST [nrows][nmodes], a FACTOR on the scalar gain, copied; nrows == 1: one vector for all environments,
+ * nrows == st->nenv: one per environment (checked where a state is at hand).  nmodes must equal the modal basis's
+ * (aomarl_set_modal first).  Entries must be finite and >= 0.  NULL: cleared, every entry point issues the launches it
+ * issued before.  All ones is the scalar law.  While gains are set:
+ *   aomarl_do_control        err = -cmat . slopes as ever (unscaled: states and rewards read it), then
+ *                            com += m2v . ((gain or the environment's gain of aomarl_set_env_gains) * mgain (.) e);
+ *                            needs aomarl_set_slopes2modes
+ *   aomarl_rl_control_modes  modes = m0 + (g * mgain[m]) * m1, in that order: with ones the bits of the scalar law
+ *   aomarl_env_step / aomarl_policy_env_step   the general chain (aomarl_rl_control_modes, aomarl_apply_control, ...,
+ *                            aomarl_do_control call by call): no fused head, small chain, residual shortcut, graph replay
+ *                            or frame pipeline.  A context with a pipelined frame in flight refuses the call. */
+int aomarl_set_modal_gains(aomarl_ctx *ctx, const float *mgain, int nrows, int nmodes);
+/* The gains as set: mgain_out HOST [nrows][nmodes] or NULL (sizes only); nrows_out = 0 when none are set. */
+int aomarl_get_modal_gains(aomarl_ctx *ctx, float *mgain_out, int *nrows_out, int *nmodes_out);
 /* volts2modes [nmodes][nactu], modes2volts [nactu][nmodes] (rlSupervisor.py:170-172),
  * freedom vector [nmodes] (rlSupervisor.py:277-278), action_modes[nact]: the modes an action
  * component drives (rlSupervisor.py:677-691); host memory */
@@ -672,6 +689,33 @@ int aomarl_roket_reset(aomarl_roket *r);
 /* x_out: DEVICE [7][nenv][nactu], the contributors of the last frame; bufs_out: DEVICE [4][nenv][nactu], its
  * noise_buf, trunc_buf, tomo_buf, mod_com.  Either may be NULL. */
 int aomarl_roket_history(aomarl_roket *r, float *x_out, float *bufs_out, void *stream);
+/* Modal gain optimisation (Gendron & Lena 1994; upstream's init_modalOpti / modalControlOptimization are not in the
+ * reference tree): a bank of loop filters over recorded OPEN-loop residual modes x[t] = -s2m . slopes (mirrors flat).
+ * For every environment, mode and candidate gain g_j it runs this simulator's loop for one mode,
+ *     e[t] = x[t] - (wa c[t-1] + wb c[t-2] + wc c[t-3]),   c[t] = c[t-1] + g_j e[t]      (history before frame 0: zero)
+ * with (wa, wb, wc) the delay-line weights of aomarl_apply_control, and sums J[env][mode][j] += e[t]^2 over t >= nskip.
+ * State and sums are double on the device; one thread owns its (series, gains) for a whole call: no atomics, no
+ * reduction across threads, the same inputs give the same bits, and a series fed in pieces gives the bits of one call.
+ * gains: HOST [ngain], copied, any finite values; delay in [0, 2]. */
+typedef struct {
+  int32_t nenv, nmodes, ngain, nskip;
+  float delay;
+  const float *gains;
+} aomarl_modopti_desc;
+typedef struct aomarl_modopti aomarl_modopti;
+int aomarl_modopti_create(const aomarl_modopti_desc *desc, aomarl_modopti **out);
+int aomarl_modopti_destroy(aomarl_modopti *m);
+/* zero filter states, sums and the frame counter (synchronises the device) */
+int aomarl_modopti_reset(aomarl_modopti *m);
+/* x_dev: DEVICE fp32, frame f of the chunk at x_dev + f * frame_stride, each an [nenv][nmodes] slab
+ * (frame_stride >= nenv * nmodes).  Asynchronous on `stream`. */
+int aomarl_modopti_accumulate(aomarl_modopti *m, const float *x_dev, int nframes, long long frame_stride, void *stream);
+/* J_out: DEVICE double [nenv][nmodes][ngain].  argmin_out: DEVICE int32 [nenv][nmodes], the index of the smallest J among
+ * the STABLE candidates (a non-finite J counts as +inf; ties, and so all-zero series, take the lowest gain; -1 when no
+ * candidate is stable).  stable_out: HOST int32 [ngain], 1 where the cubic of that gain has all roots inside the unit
+ * circle (g = 0, the open loop, counts as stable).  frames_out: HOST, frames accumulated so far.  Any may be NULL. */
+int aomarl_modopti_result(aomarl_modopti *m, double *J_out, int32_t *argmin_out, int32_t *stable_out,
+                          long long *frames_out, void *stream);
 /* PSF reconstruction from the covariance of the ROKET error buffers, the Vii algorithm (guardians/gamora.py:24-100
  * psf_rec_Vii, :103-171 psf_rec_vii_cpu).  For the eigenpairs (e_k, V_k) of the modal covariance and the phase maps
  * m_k = IF^T (Btt V_k)[:-2] + TT (Btt V_k)[-2:] on the lit pixels of a p x p pupil, zero-padded to N x N (:148-159):
