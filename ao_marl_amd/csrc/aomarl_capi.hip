@@ -4,6 +4,7 @@
 // aomarl_create / aomarl_set_* (aomarl_reset uploads env_count seeds, 4 bytes each).
 #include "aomarl_kernels.hip"
 #include "aomarl_qf4_host.h"
+#include "aomarl_step_plan_host.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -46,7 +47,6 @@ struct aomarl_ctx {
   hipEvent_t ride_ev = nullptr;        // frame pipeline: the event a whole-batch one-launch move may carry on its dispatch
   bool rode = false;                   // ... and whether it did
   int residual_shortcut = 0;           // "residual_shortcut": aomarl_env_step takes the residual modes from ONE product with v2m . cmat (aomarl_set_slopes2modes)
-  bool skip_do_control = false;        // (aomarl_env_step's small chain: aomarl_next_part_one leaves do_control to its tail kernel)
   int small_move = 1;                  // "small_move": 1 = one k_move_small launch per frame's move where the screens allow it
   bool small_ok = false;               // every layer has dim <= MOVE_SMALL_DIM, ns + dim <= MOVE_SMALL_K (transposed [A|B] uploaded)
   int reset_streams = 2;               // "reset_streams": a batch reset in that many parts side by side, one stream each (1..4)
@@ -184,6 +184,7 @@ static int fw_ev_rewind(aomarl_ctx *c) {
   return 0;
 }
 static int frame_fused_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, int flags, void *stream, int slot);
+static int next_part_one_sense(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accumx, float *accumy, int image_flags, void *stream);
 
 static unsigned long long g_cfg_epoch = 0;      // process-wide options / precision changes (see aomarl_ctx::cfg_epoch)
 const char *aomarl_last_error(void) { return g_err; }

@@ -262,6 +262,29 @@ int aomarl_policy_sample(int nenv, int act_max, int action_dim, const float *hea
   return 0;
 }
 
+// the blocks as k_assemble_state and k_small_tail read them (no split-K part)
+static int state_blocks_fill(int nblocks, const float *const *src, const int32_t *ld, const int32_t *dim,
+                             const float *const *mean, const float *const *std_, const int32_t *sel, StateBlocks *out) {
+  if (!src || !ld || !dim) return fail("assemble_state: null pointer");
+  if (nblocks < 1 || nblocks > 8) return fail("assemble_state: 1..8 blocks");
+  StateBlocks &sb = *out;
+  int off = 0;
+  for (int k = 0; k < 8; k++) {
+    const bool on = k < nblocks;
+    sb.src[k] = on ? src[k] : nullptr; sb.ld[k] = on ? ld[k] : 0; sb.dim[k] = on ? dim[k] : 0;
+    sb.mean[k] = (on && mean) ? mean[k] : nullptr; sb.std[k] = (on && std_) ? std_[k] : nullptr;
+    sb.off[k] = off;
+    if (on) {
+      if (!src[k] || dim[k] <= 0 || (!sel && ld[k] < dim[k])) return fail("assemble_state: bad block %d", k);
+      if ((sb.mean[k] == nullptr) != (sb.std[k] == nullptr)) return fail("assemble_state: mean/std must come together");
+      off += dim[k];
+    }
+  }
+  sb.nblocks = nblocks; sb.total = off; sb.sel = sel;
+  sb.part = nullptr; sb.nsplit = 0; sb.pn = 0; sb.alpha = 1.f; sb.sum_out = nullptr;
+  return 0;
+}
+
 struct AssemblePart { const float *part; int nsplit, pn; float alpha; float *sum_out; };
 static int assemble_state_impl(int nenv, int nblocks, const float *const *src, const int32_t *ld,
                                const int32_t *dim, const float *const *mean, const float *const *std_,
@@ -282,30 +305,17 @@ int aomarl_assemble_state_cols(int nenv, int nblocks, const float *const *src, c
 static int assemble_state_impl(int nenv, int nblocks, const float *const *src, const int32_t *ld,
                                const int32_t *dim, const float *const *mean, const float *const *std_,
                                const int32_t *sel, float *out, void *stream, const AssemblePart *pt) {
-  if (!src || !ld || !dim || !out) return fail("assemble_state: null pointer");
-  if (nblocks < 1 || nblocks > 8) return fail("assemble_state: 1..8 blocks");
+  if (!out) return fail("assemble_state: null pointer");
   StateBlocks sb;
-  int off = 0;
-  for (int k = 0; k < 8; k++) {
-    const bool on = k < nblocks;
-    sb.src[k] = on ? src[k] : nullptr; sb.ld[k] = on ? ld[k] : 0; sb.dim[k] = on ? dim[k] : 0;
-    sb.mean[k] = (on && mean) ? mean[k] : nullptr; sb.std[k] = (on && std_) ? std_[k] : nullptr;
-    sb.off[k] = off;
-    if (on) {
-      if (!src[k] || dim[k] <= 0 || (!sel && ld[k] < dim[k])) return fail("assemble_state: bad block %d", k);
-      if ((sb.mean[k] == nullptr) != (sb.std[k] == nullptr)) return fail("assemble_state: mean/std must come together");
-      off += dim[k];
-    }
-  }
-  sb.nblocks = nblocks; sb.total = off; sb.sel = sel;
-  sb.part = nullptr; sb.nsplit = 0; sb.pn = 0; sb.alpha = 1.f; sb.sum_out = nullptr;
+  int rc = state_blocks_fill(nblocks, src, ld, dim, mean, std_, sel, &sb);
+  if (rc) return rc;
   int extra = 0;
   if (pt && pt->part && pt->nsplit > 0) {
     sb.part = pt->part; sb.nsplit = pt->nsplit; sb.pn = pt->pn; sb.alpha = pt->alpha; sb.sum_out = pt->sum_out;
     extra = pt->pn;
   }
   if (nenv <= 0) return 0;
-  hipLaunchKernelGGL(k_assemble_state, dim3((off + extra + 255) / 256, nenv), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_assemble_state, dim3((sb.total + extra + 255) / 256, nenv), dim3(256), 0, (hipStream_t)stream,
                      nenv, sb, out);
   LAUNCHCHK();
   return 0;

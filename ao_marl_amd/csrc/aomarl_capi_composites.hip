@@ -163,8 +163,9 @@ int aomarl_materialize_dm_shape(aomarl_ctx *c, aomarl_state *st, int b, int n, v
   return dm_shape_impl(c, st, b, n, nullptr, false, stream);
 }
 
-int aomarl_next_part_one(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accumx, float *accumy,
-                         int image_flags, void *stream) {
+// aomarl_next_part_one up to the slopes: everything but do_control (aomarl_env_step's tail does what its plan says)
+static int next_part_one_sense(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accumx, float *accumy,
+                               int image_flags, void *stream) {
   int rc = aomarl_move_atmos(c, st, b, n, accumx, accumy, stream);
   if (rc) return rc;
   int fl = (image_flags | AOMARL_IMG_COG | AOMARL_IMG_NOISE) & ~(AOMARL_IMG_NO_ATMOS | AOMARL_IMG_NO_DMS);
@@ -183,8 +184,7 @@ int aomarl_next_part_one(aomarl_ctx *c, aomarl_state *st, int b, int n, float *a
       rc = prefetch_atmos_impl(c, st, b, n, accumx, accumy, stream, c->frame_marked);
       if (rc) return rc;
     }
-    if (c->skip_do_control) return 0;
-    return aomarl_do_control(c, st, b, n, stream);
+    return 0;
   }
   rc = aomarl_target_psf(c, st, b, n, stream);
   if (rc) return rc;
@@ -199,7 +199,13 @@ int aomarl_next_part_one(aomarl_ctx *c, aomarl_state *st, int b, int n, float *a
     rc = aomarl_prefetch_atmos(c, st, b, n, accumx, accumy, stream);
     if (rc) return rc;
   }
-  if (c->skip_do_control) return 0;
+  return 0;
+}
+
+int aomarl_next_part_one(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accumx, float *accumy,
+                         int image_flags, void *stream) {
+  const int rc = next_part_one_sense(c, st, b, n, accumx, accumy, image_flags, stream);
+  if (rc) return rc;
   return aomarl_do_control(c, st, b, n, stream);
 }
 

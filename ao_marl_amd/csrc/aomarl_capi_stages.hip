@@ -483,11 +483,9 @@ int aomarl_apply_control(aomarl_ctx *c, aomarl_state *st, int b, int n, int comp
   int rc = check_range(c, st, b, n);
   if (rc) return rc;
   if (n == 0) return 0;
-  const float d = c->delay;
-  float wa, wb, wc;
-  if (d <= 1.f) { wa = 1.f - d; wb = d; wc = 0.f; } else { wa = 0.f; wb = 2.f - d; wc = d - 1.f; }
+  const DelayWeights dw = delay_weights(c->delay, false);
   const int na = c->sys.nactu;
-  hipLaunchKernelGGL(k_delay, dim3((na + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, dev_state(st), na, st->ld_actu, wa, wb, wc, b, comp_voltage & AOMARL_APPLY_COMP_VOLTAGE);
+  hipLaunchKernelGGL(k_delay, dim3((na + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, dev_state(st), na, st->ld_actu, dw.wa, dw.wb, dw.wc, b, comp_voltage & AOMARL_APPLY_COMP_VOLTAGE);
   LAUNCHCHK();
   const bool defer = (comp_voltage & AOMARL_APPLY_DEFER_STACK_SHAPE) && aomarl_dm_from_voltage_available(c);
   return dm_shape_impl(c, st, b, n, nullptr, defer, stream);

@@ -122,7 +122,7 @@ static int env_step_validate(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g
 //   k_small_tail: -cmat . s, integrator, v2m . err, the state blocks
 // Same formulas as the kernels they stand for; the sums of the products run in one thread each, in index order
 // (the split-K GEMM sums tiles): fp32 round-off apart, the same numbers ("small_chain" = 0: the general chain).
-constexpr int SMALL_NM = 512, SMALL_NA = 512, SMALL_NSL = 1024;
+// (SMALL_NM, SMALL_NA, SMALL_NSL: aomarl_step_plan_host.h, with the rule that says when this chain runs)
 // y[o] = sum_k x[k] W[o][k] for o < no, x in LDS, by the whole block: FOUR threads per output (they read 16
 // consecutive bytes of the row per step, two accumulators each, then two xor-shuffles), blockDim.x / 4 outputs per pass.
 // done(o, y) runs in the first thread of each quad.
@@ -244,21 +244,34 @@ __global__ __launch_bounds__(256) void k_small_tail(DevState st, SmallTail p, St
   }
 }
 
-static bool small_chain_ok(const aomarl_ctx *c, const aomarl_env_glue *g) {
-  return c->small_chain && c->sys.nactu <= SMALL_NA && c->sys.nslope <= SMALL_NSL && g->nmodes <= SMALL_NM &&
-         (long long)c->sys.nactu * c->sys.nslope <= 65536 && c->cmat && !c->env_gain && !c->mgain;
-}
-
-// may the chain run in its fused form?  (ktt: index of the tip-tilt mirror)
-static bool env_step_fusable(aomarl_ctx *c, const aomarl_env_glue *g, int *ktt_out) {
-  int ktt = -1, ntt = 0, nother = 0;
+// Everything step_plan (aomarl_step_plan_host.h) decides from, read off the context, the glue and the call's arguments:
+// the one place that looks at these fields to choose a chain.  st may be null (aomarl_env_step_shortcut: no state at
+// hand, no pipeline).
+static StepFacts step_facts(aomarl_ctx *c, const aomarl_state *st, const aomarl_env_glue *g, const float *accumx,
+                            const float *accumy) {
+  StepFacts f;
+  int ntt = 0, nother = 0;
+  f.ktt = -1;
   for (int k = 0; k < c->ndm; k++) {
-    if (c->sys.dms[k].type == AOMARL_DM_TT) { ktt = k; ntt++; } else nother++;
+    if (c->sys.dms[k].type == AOMARL_DM_TT) { f.ktt = k; ntt++; } else nother++;
   }
-  const bool defer = c->defer_dm_shape && aomarl_dm_from_voltage_available(c);
-  if (ktt_out) *ktt_out = ktt;
-  // (modal gains, aomarl_set_modal_gains: the general chain -- aomarl_rl_control_modes and aomarl_do_control apply them)
-  return !(g->flags & AOMARL_ENV_STEP_UNFUSED) && ntt == 1 && (defer || nother == 0) && !c->mgain;
+  f.unfused = (g->flags & AOMARL_ENV_STEP_UNFUSED) != 0;
+  f.one_tt = ntt == 1; f.no_other_dm = nother == 0;
+  f.defer_shape = c->defer_dm_shape && aomarl_dm_from_voltage_available(c);
+  f.mgain = c->mgain != nullptr; f.env_gain = c->env_gain != nullptr;
+  f.small_opt = c->small_chain != 0;
+  f.nactu = c->sys.nactu; f.nslope = c->sys.nslope; f.nmodes = g->nmodes;
+  f.cmat = c->cmat != nullptr;
+  f.shortcut_opt = c->residual_shortcut != 0;
+  f.s2m_match = c->s2m && c->s2m_nmodes == g->nmodes;
+  f.denoiser = g->denoiser != nullptr;
+  const auto &P = c->pipe;
+  f.twin = P.have_twin; f.pipe_opt = c->pipe_enabled; f.owner = st && P.owner_screens == st->screens;
+  f.prefetch = c->prefetch_atmos; f.delay_one = c->delay == 1.f; f.noiseless = c->sys.noise < 0.f;
+  f.accum = accumx && accumy; f.subpixel = c->subpixel_flow; f.frame_fused = aomarl_frame_fused_available(c) != 0;
+  f.in_flight = P.active && f.owner;
+  f.graph_step = c->graph_step; f.capturing = c->capturing;
+  return f;
 }
 
 // ---- AoEnv.rl_step, fused form: Btt correction from the coordinates at hand (+ the per-agent rewards of the
@@ -266,8 +279,9 @@ static bool env_step_fusable(aomarl_ctx *c, const aomarl_env_glue *g, int *ktt_o
 // `stv`: the state whose voltage / dm_shape / pending PSF window this call writes and commits (st itself, or
 // the frame pipeline's view of the parity the NEXT frame uses).  ahead: the delay line is evaluated one frame
 // ahead (the voltages of the frame that follows the one in flight): weights shifted by one command.
+// head: HEAD_SMALL (k_small_head) or HEAD_FUSED, as the caller's plan says.
 static int env_step_head_fused(aomarl_ctx *c, aomarl_state *st, aomarl_state *stv, aomarl_env_glue *g, const float *action,
-                               float gain, float *reward_out, int ktt, bool ahead, hipEvent_t psf_ev, void *stream) {
+                               float gain, float *reward_out, HeadKind head, int ktt, bool ahead, hipEvent_t psf_ev, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   const int n = st->nenv, nm = g->nmodes, R = g->nhist + 1, na = c->sys.nactu;
   const size_t slot = (size_t)n * nm;
@@ -275,11 +289,10 @@ static int env_step_head_fused(aomarl_ctx *c, aomarl_state *st, aomarl_state *st
   float *mnew = g->modes_ring + (size_t)((g->ring_pos + 1) % R) * slot;
   Work w = work_layout(c, st->nenv);
   DevState dsv = dev_state(stv);
-  if (small_chain_ok(c, g)) {
-    const float d = c->delay;
+  const DelayWeights dw = delay_weights(c->delay, ahead);
+  if (head == HEAD_SMALL) {
     SmallHead p;
-    if (d <= 1.f) { p.wa = 1.f - d; p.wb = d; p.wc = 0.f; } else { p.wa = 0.f; p.wb = 2.f - d; p.wc = d - 1.f; }
-    if (ahead) { p.wa = p.wb; p.wb = p.wc; p.wc = 0.f; }
+    p.wa = dw.wa; p.wb = dw.wb; p.wc = dw.wc;
     p.nm = nm; p.na = na; p.nact = c->nact; p.n_agents = reward_out ? g->n_agents : 0; p.ld_m2v = c->ld_m2v;
     p.ld_actu = st->ld_actu; p.ktt = ktt; p.do_strehl = 1; p.gain = gain; p.factor = g->reward_factor;
     p.m0 = newest; p.m1 = g->res_modes; p.action = action; p.freedom = c->freedom; p.m2v = c->m2v;
@@ -312,9 +325,6 @@ static int env_step_head_fused(aomarl_ctx *c, aomarl_state *st, aomarl_state *st
   const int nsp = gd.slabs;
   const float alpha = gd.slab_alpha;
   LAUNCHCHK();
-  const float d = c->delay;
-  float wa, wb, wc;
-  if (d <= 1.f) { wa = 1.f - d; wb = d; wc = 0.f; } else { wa = 0.f; wb = 2.f - d; wc = d - 1.f; }
   if (ahead) {
     // delay == 1 (the pipeline's condition): v(t+1) = c(t); the tip-tilt slot in the same launch, and the frame
     // stream released right behind it -- the Strehl commit below is not on the frame kernel's path
@@ -325,10 +335,10 @@ static int env_step_head_fused(aomarl_ctx *c, aomarl_state *st, aomarl_state *st
     c->pipe.cmd_covers_psf = psf_waited;
   } else {
     if (nsp > 0)
-      hipLaunchKernelGGL(k_delay_sum, dim3((na + 255) / 256, n), dim3(256), 0, s, dsv, na, st->ld_actu, wa, wb, wc, 0, 1,
+      hipLaunchKernelGGL(k_delay_sum, dim3((na + 255) / 256, n), dim3(256), 0, s, dsv, na, st->ld_actu, dw.wa, dw.wb, dw.wc, 0, 1,
                          st->work + w.GEMM, nsp, alpha, n);
     else
-      hipLaunchKernelGGL(k_delay, dim3((na + 255) / 256, n), dim3(256), 0, s, dsv, na, st->ld_actu, wa, wb, wc, 0, 1);
+      hipLaunchKernelGGL(k_delay, dim3((na + 255) / 256, n), dim3(256), 0, s, dsv, na, st->ld_actu, dw.wa, dw.wb, dw.wc, 0, 1);
     LAUNCHCHK();
   }
   if (psf_ev) { if (!psf_waited) HIPCHK(hipStreamWaitEvent(s, psf_ev, 0)); }
@@ -340,107 +350,104 @@ static int env_step_head_fused(aomarl_ctx *c, aomarl_state *st, aomarl_state *st
   return 0;
 }
 
-// the residual shortcut applies: the matrix is there for these modes and the integrator gain is one scalar
-static bool env_step_shortcut(const aomarl_ctx *c, const aomarl_env_glue *g) {
-  return c->residual_shortcut && c->s2m && c->s2m_nmodes == g->nmodes && !c->env_gain && !c->mgain;
+// the state blocks of one step: the command histories oldest first, the newest command (ring slot nxt), the residual
+struct StepBlocks {
+  const float *src[8], *mean[8], *sd[8];
+  int32_t ld[8], dim[8];
+  int nb;
+  bool norm;                       // standardised (all four of the glue's mean / std arrays, or none)
+};
+static StepBlocks step_blocks(const aomarl_env_glue *g, int n, int nxt) {
+  const int nm = g->nmodes, R = g->nhist + 1;
+  const size_t slot = (size_t)n * nm;
+  StepBlocks B;
+  B.nb = 0;
+  auto add = [&](const float *src, const float *mean, const float *sd) {
+    B.src[B.nb] = src; B.mean[B.nb] = mean; B.sd[B.nb] = sd; B.ld[B.nb] = nm; B.dim[B.nb] = g->dm_dim; B.nb++;
+  };
+  for (int h = g->nhist; h >= 1; h--) add(g->modes_ring + (size_t)((nxt - h + R * 8) % R) * slot, g->mean_dm, g->std_dm);
+  add(g->modes_ring + (size_t)nxt * slot, g->mean_dm, g->std_dm);
+  add(g->res_modes, g->mean_res, g->std_res);
+  B.norm = g->mean_dm && g->std_dm && g->mean_res && g->std_res;
+  return B;
 }
 
-// ---- the rest of AoEnv.linear_step behind do_control: v2m . err, the state blocks
-// s2m_view: the residual shortcut -- the caller has NOT run do_control; the residual modes come from that state's slopes
-// in one product with -(v2m . cmat) (the integrator lives in the Btt coordinates, the next head rebuilds the command)
-static int env_step_tail(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, bool fused, float *state_out, void *stream,
-                         const aomarl_state *slopes_view = nullptr, const aomarl_state *s2m_view = nullptr) {
+// a product of the tail, res_modes[n][nm] = alpha A . B^T, left as split-K slabs for the kernel that assembles the
+// state (part: how that kernel sums them)
+static int tail_slab_product(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, int K, float alpha, const float *A, int lda,
+                             const float *B, int ldb, float scale_b, hipStream_t s, AssemblePart *part) {
+  const int n = st->nenv, nm = g->nmodes;
+  Work w = work_layout(c, n);
+  GemmArgs ga(n, nm, K, alpha, A, lda, B, ldb, 0.0f, g->res_modes, nm, s);
+  ga.ws = st->work + w.GEMM; ga.ws_floats = w.gemm_floats; ga.slabs_only = true; ga.min_chunk = 288;
+  ga.fast = true; ga.sb = scale_b;
+  const GemmDone gd = launch_gemm_nt(ga);
+  LAUNCHCHK();
+  if (gd.slabs > 0) *part = {st->work + w.GEMM, gd.slabs, nm, gd.slab_alpha, g->res_modes};
+  return 0;
+}
+
+// ---- the rest of AoEnv.linear_step behind the slopes: do_control where the tail has one of its own, v2m . err, the
+// state blocks.  view: the state whose slopes are reduced (st itself, or the frame pipeline's view of the parity whose
+// frame is done).
+static int env_step_tail(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, TailKind kind, aomarl_state *view,
+                         float *state_out, void *stream) {
   hipStream_t s = (hipStream_t)stream;
-  const int n = st->nenv, nm = g->nmodes, R = g->nhist + 1, na = c->sys.nactu;
-  const size_t slot = (size_t)n * nm;
-  const int nxt = (g->ring_pos + 1) % R;
-  float *mnew = g->modes_ring + (size_t)nxt * slot;
-  Work w = work_layout(c, st->nenv);
+  const int n = st->nenv, nm = g->nmodes, na = c->sys.nactu, nsl = c->sys.nslope;
+  const int nxt = (g->ring_pos + 1) % (g->nhist + 1);
   int rc = 0;
-  if (slopes_view) {
-    // small systems: do_control, v2m . err and the state blocks in ONE kernel (the caller has NOT run do_control)
-    const float *src[8], *mean[8], *sd[8];
-    int32_t ld[8], dim[8];
-    int nb = 0;
-    for (int h = g->nhist; h >= 1; h--) {
-      src[nb] = g->modes_ring + (size_t)((nxt - h + R * 8) % R) * slot;
-      mean[nb] = g->mean_dm; sd[nb] = g->std_dm; ld[nb] = nm; dim[nb] = g->dm_dim; nb++;
-    }
-    src[nb] = mnew; mean[nb] = g->mean_dm; sd[nb] = g->std_dm; ld[nb] = nm; dim[nb] = g->dm_dim; nb++;
-    src[nb] = g->res_modes; mean[nb] = g->mean_res; sd[nb] = g->std_res; ld[nb] = nm; dim[nb] = g->dm_dim; nb++;
-    const bool norm = g->mean_dm && g->std_dm && g->mean_res && g->std_res;
+  if (tail_runs_do_control(kind)) {
+    rc = aomarl_do_control(c, view, 0, n, stream);
+    if (rc) return rc;
+  }
+  const StepBlocks B = step_blocks(g, n, nxt);
+  const float *const *mean = B.norm ? B.mean : nullptr, *const *sd = B.norm ? B.sd : nullptr;
+  AssemblePart part = {nullptr, 0, 0, 1.f, nullptr};
+  switch (kind) {
+  case TAIL_SMALL: {               // do_control, v2m . err and the state blocks in ONE kernel
     StateBlocks sb;
-    int off = 0;
-    for (int k = 0; k < 8; k++) {
-      const bool on = k < nb;
-      sb.src[k] = on ? src[k] : nullptr; sb.ld[k] = on ? ld[k] : 0; sb.dim[k] = on ? dim[k] : 0;
-      sb.mean[k] = (on && norm) ? mean[k] : nullptr; sb.std[k] = (on && norm) ? sd[k] : nullptr;
-      sb.off[k] = off;
-      if (on) off += dim[k];
-    }
-    sb.nblocks = nb; sb.total = off; sb.sel = g->sel;
-    sb.part = nullptr; sb.nsplit = 0; sb.pn = 0; sb.alpha = 1.f; sb.sum_out = nullptr;
+    rc = state_blocks_fill(B.nb, B.src, B.ld, B.dim, mean, sd, g->sel, &sb);
+    if (rc) return rc;
     SmallTail p;
-    p.nsl = c->sys.nslope; p.na = na; p.nm = nm; p.ld_cmat = c->ld_cmat; p.ld_v2m = c->ld_v2m; p.ld_actu = st->ld_actu;
+    p.nsl = nsl; p.na = na; p.nm = nm; p.ld_cmat = c->ld_cmat; p.ld_v2m = c->ld_v2m; p.ld_actu = st->ld_actu;
     p.gain = c->gain; p.cmat = c->cmat; p.v2m = c->v2m; p.res_modes = g->res_modes;
-    hipLaunchKernelGGL(k_small_tail, dim3(n), dim3(256), 0, s, dev_state(slopes_view), p, sb, state_out);
+    hipLaunchKernelGGL(k_small_tail, dim3(n), dim3(256), 0, s, dev_state(view), p, sb, state_out);
     LAUNCHCHK();
     g->ring_pos = nxt;
     return 0;
   }
-  AssemblePart part = {nullptr, 0, 0, 1.f, nullptr};
-  if (s2m_view) {
-    const int nsl = c->sys.nslope;
-    GemmArgs ga(n, nm, nsl, -1.0f, s2m_view->slopes, nsl, c->s2m, c->ld_cmat, 0.0f, g->res_modes, nm, s);
-    ga.ws = st->work + w.GEMM; ga.ws_floats = w.gemm_floats; ga.slabs_only = true; ga.min_chunk = 288;
-    ga.fast = true; ga.sb = c->s2m_scale;                    /* slopes (arcsec), unscaled */
-    const GemmDone gd = launch_gemm_nt(ga);
-    LAUNCHCHK();
-    if (gd.slabs > 0) { part.part = st->work + w.GEMM; part.nsplit = gd.slabs; part.pn = nm; part.alpha = gd.slab_alpha; part.sum_out = g->res_modes; }
-  } else if (fused) {
-    GemmArgs ga(n, nm, na, 1.0f, st->err, st->ld_actu, c->v2m, c->ld_v2m, 0.0f, g->res_modes, nm, s);
-    ga.ws = st->work + w.GEMM; ga.ws_floats = w.gemm_floats; ga.slabs_only = true; ga.min_chunk = 288;
-    ga.fast = true; ga.sb = c->v2m_scale;                    /* volts */
-    const GemmDone gd = launch_gemm_nt(ga);
-    LAUNCHCHK();
-    if (gd.slabs > 0) { part.part = st->work + w.GEMM; part.nsplit = gd.slabs; part.pn = nm; part.alpha = gd.slab_alpha; part.sum_out = g->res_modes; }
-  } else {
+  case TAIL_SHORTCUT:              // the residual modes from the slopes in one product with -(v2m . cmat); slopes (arcsec), unscaled
+    rc = tail_slab_product(c, st, g, nsl, -1.0f, view->slopes, nsl, c->s2m, c->ld_cmat, c->s2m_scale, s, &part);
+    break;
+  case TAIL_FUSED:                 // volts
+    rc = tail_slab_product(c, st, g, na, 1.0f, st->err, st->ld_actu, c->v2m, c->ld_v2m, c->v2m_scale, s, &part);
+    break;
+  case TAIL_STAGES:
     rc = aomarl_volts2modes(c, st, n, st->err, st->ld_actu, g->res_modes, stream);
-    if (rc) return rc;
+    break;
   }
-  const float *src[8], *mean[8], *sd[8];
-  int32_t ld[8], dim[8];
-  int nb = 0;
-  for (int h = g->nhist; h >= 1; h--) {                       // oldest first
-    src[nb] = g->modes_ring + (size_t)((nxt - h + R * 8) % R) * slot;
-    mean[nb] = g->mean_dm; sd[nb] = g->std_dm; ld[nb] = nm; dim[nb] = g->dm_dim; nb++;
-  }
-  src[nb] = mnew; mean[nb] = g->mean_dm; sd[nb] = g->std_dm; ld[nb] = nm; dim[nb] = g->dm_dim; nb++;
-  src[nb] = g->res_modes; mean[nb] = g->mean_res; sd[nb] = g->std_res; ld[nb] = nm; dim[nb] = g->dm_dim; nb++;
-  const bool norm = g->mean_dm && g->std_dm && g->mean_res && g->std_res;
-  rc = assemble_state_impl(n, nb, src, ld, dim, norm ? mean : nullptr, norm ? sd : nullptr, g->sel, state_out, stream,
-                           &part);
+  if (rc) return rc;
+  rc = assemble_state_impl(n, B.nb, B.src, B.ld, B.dim, mean, sd, g->sel, state_out, stream, &part);
   if (rc) return rc;
   g->ring_pos = nxt;
   return 0;
 }
 
 static int env_step_body(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const float *action, float gain,
-                         float *accumx, float *accumy, float *state_out, float *reward_out, void *stream) {
+                         float *accumx, float *accumy, float *state_out, float *reward_out, const StepFacts &f,
+                         const StepPlan &plan, void *stream) {
   int rc = env_step_validate(c, st, g, action, state_out, reward_out);
   if (rc) return rc;
   const int n = st->nenv, nm = g->nmodes, R = g->nhist + 1;
   const size_t slot = (size_t)n * nm;
   float *newest = g->modes_ring + (size_t)g->ring_pos * slot;
   float *mnew = g->modes_ring + (size_t)((g->ring_pos + 1) % R) * slot;
-  // Fused form of the chain (same arithmetic, same order of every sum -- the results are bit for bit
-  // those of the entry points called one by one): every split-K reduction happens in the kernel that
-  // consumes the product, independent small kernels share a launch.  10 launches per step on the
-  // main stream instead of 14.
-  int ktt = -1;
-  const bool fused = env_step_fusable(c, g, &ktt);
-  if (fused) {
-    rc = env_step_head_fused(c, st, st, g, action, gain, reward_out, ktt, false, nullptr, stream);
+  if (plan.head != HEAD_STAGES) {
+    // Fused form of the chain (same arithmetic, same order of every sum -- the results are bit for bit
+    // those of the entry points called one by one): every split-K reduction happens in the kernel that
+    // consumes the product, independent small kernels share a launch.  10 launches per step on the
+    // main stream instead of 14.
+    rc = env_step_head_fused(c, st, st, g, action, gain, reward_out, plan.head, f.ktt, false, nullptr, stream);
     if (rc) return rc;
   } else {
     // ---- AoEnv.rl_step: Btt correction from the coordinates at hand, delay line, Strehl
@@ -457,7 +464,7 @@ static int env_step_body(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, co
     }
   }
   // ---- AoEnv.linear_step
-  if (g->denoiser) {
+  if (plan.sense == SENSE_DENOISER) {
     // rlSupervisor.py:975-984: image -> autoencoder -> centroids -> do_control, the cube staying on the device
     if (!st->bincube) return fail("env_step: the denoiser needs st->bincube");
     if (!aomarl_frame_fused_available(c)) return fail("env_step: denoiser branch needs the one-pass frame kernel");
@@ -477,20 +484,11 @@ static int env_step_body(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, co
       if (rc) return rc;
     }
     rc = aomarl_do_centroids(c, st, 0, n, stream);
-    if (rc) return rc;
-    rc = aomarl_do_control(c, st, 0, n, stream);
   } else {
-    const bool small = fused && small_chain_ok(c, g);
-    const bool shortcut = !small && fused && env_step_shortcut(c, g);
-    c->skip_do_control = small || shortcut;      // the small chain's tail kernel does it; the shortcut needs none
-    rc = aomarl_next_part_one(c, st, 0, n, accumx, accumy, 0, stream);
-    c->skip_do_control = false;
-    if (rc) return rc;
-    if (small) return env_step_tail(c, st, g, fused, state_out, stream, st);
-    if (shortcut) return env_step_tail(c, st, g, fused, state_out, stream, nullptr, st);
+    rc = next_part_one_sense(c, st, 0, n, accumx, accumy, 0, stream);
   }
   if (rc) return rc;
-  return env_step_tail(c, st, g, fused, state_out, stream);
+  return env_step_tail(c, st, g, plan.tail, st, state_out, stream);
 }
 
 // ---------------------------------------------------------------- frame pipeline (aomarl_set_frame_pipeline)
@@ -507,15 +505,6 @@ static aomarl_state pipe_view(aomarl_ctx *c, const aomarl_state *st, int par) {
     v.work = c->pipe.twin.work;
   }
   return v;
-}
-
-static bool pipe_eligible(aomarl_ctx *c, const aomarl_state *st, const aomarl_env_glue *g, const float *accumx,
-                          const float *accumy) {
-  const auto &P = c->pipe;
-  return P.have_twin && c->pipe_enabled && P.owner_screens == st->screens && !c->graph_step && !c->capturing && c->prefetch_atmos &&
-         c->delay == 1.f && c->sys.noise < 0.f && !g->denoiser && accumx && accumy && !c->subpixel_flow &&
-         aomarl_frame_fused_available(c) && c->defer_dm_shape && aomarl_dm_from_voltage_available(c) &&
-         env_step_fusable(c, g, nullptr) && !c->mgain;
 }
 
 static int pipe_init(aomarl_ctx *c, const aomarl_state *st) {
@@ -591,15 +580,14 @@ static int pipe_prefetch(aomarl_ctx *c, aomarl_state *st, float *accumx, float *
 }
 
 static int env_step_pipelined(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const float *action, float gain,
-                              float *accumx, float *accumy, float *state_out, float *reward_out, void *stream) {
+                              float *accumx, float *accumy, float *state_out, float *reward_out, const StepFacts &f,
+                              const StepPlan &plan, void *stream) {
   auto &P = c->pipe;
   hipStream_t s = (hipStream_t)stream;
-  const int n = st->nenv;
-  int ktt = -1;
-  env_step_fusable(c, g, &ktt);
+  const int n = st->nenv, ktt = f.ktt;
   if (!P.active) {
     // ---- first step: the plain order, then the next frame ahead
-    int rc = env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, stream);
+    int rc = env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, f, plan, stream);
     if (rc) return rc;
     if (!c->premoved || !c->psf_side) return 0;      // (the plain step did not leave the steady state behind: stay plain)
     rc = pipe_init(c, st);
@@ -636,7 +624,7 @@ static int env_step_pipelined(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *
   int rc = env_step_validate(c, st, g, action, state_out, reward_out);
   aomarl_state vq = pipe_view(c, st, q), vp = pipe_view(c, st, p);
   hipEvent_t pe = P.psf_out[q] ? P.ev_psf[q] : nullptr;     // the PSF finish of the last frame of parity q
-  if (!rc) rc = env_step_head_fused(c, st, &vq, g, action, gain, reward_out, ktt, true, pe, stream);
+  if (!rc) rc = env_step_head_fused(c, st, &vq, g, action, gain, reward_out, plan.head, ktt, true, pe, stream);
   // the frame stream is released behind k_delay_ahead, in front of the Strehl commit.  The frame kernel overwrites the
   // PSF rows that parity's last PSF finish reads: the chain waited for that finish in front of its first kernel
   // (cmd_covers_psf; the small chain's one kernel waits for it too: cmd_covers_commit), else the frame stream does
@@ -645,12 +633,7 @@ static int env_step_pipelined(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *
   if (!rc) rc = pipe_prefetch(c, st, accumx, accumy, p, q);
   // ---- reduce frame p
   if (!rc && hipStreamWaitEvent(s, P.ev_done_cur[p], 0) != hipSuccess) rc = fail("frame pipeline: hipStreamWaitEvent failed");
-  if (!rc && small_chain_ok(c, g)) rc = env_step_tail(c, st, g, true, state_out, stream, &vp);
-  else if (!rc && env_step_shortcut(c, g)) rc = env_step_tail(c, st, g, true, state_out, stream, nullptr, &vp);
-  else {
-    if (!rc) rc = aomarl_do_control(c, &vp, 0, n, stream);
-    if (!rc) rc = env_step_tail(c, st, g, true, state_out, stream);
-  }
+  if (!rc) rc = env_step_tail(c, st, g, plan.tail, &vp, state_out, stream);
   c->pipe_internal = false;
   if (rc) return rc;
   P.par = q; P.steps++;
@@ -750,19 +733,21 @@ int aomarl_do_control_reduced(aomarl_ctx *c, aomarl_state *st, void *stream) {
 
 int aomarl_env_step_shortcut(aomarl_ctx *c, const aomarl_env_glue *g) {
   if (!c || !g) return 0;
-  return (!g->denoiser && env_step_fusable(c, g, nullptr) && !small_chain_ok(c, g) && env_step_shortcut(c, g)) ? 1 : 0;
+  return step_plan(step_facts(c, nullptr, g, nullptr, nullptr)).tail == TAIL_SHORTCUT ? 1 : 0;     // (never with a denoiser)
 }
 
 int aomarl_env_step(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const float *action, float gain,
                     float *accumx, float *accumy, float *state_out, float *reward_out, void *stream) {
   if (!c || !st || !g || !state_out) return fail("env_step: null argument");
-  if (pipe_eligible(c, st, g, accumx, accumy))
-    return env_step_pipelined(c, st, g, action, gain, accumx, accumy, state_out, reward_out, stream);
-  if (c->pipe.active && c->pipe.owner_screens == st->screens)
+  const StepFacts f = step_facts(c, st, g, accumx, accumy);
+  const StepPlan sp = step_plan(f);
+  if (sp.route == PIPELINED)
+    return env_step_pipelined(c, st, g, action, gain, accumx, accumy, state_out, reward_out, f, sp, stream);
+  if (sp.route == REFUSED_IN_FLIGHT)
     return fail("env_step: a pipelined frame is in flight but this call is not eligible for the frame pipeline "
                 "(options, glue or arguments changed within an episode, or aomarl_set_modal_gains): reset first");
-  // (modal gains: no replay -- the general chain, launched call by call)
-  if (!c->graph_step || c->capturing || c->mgain) return env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, stream);
+  if (sp.route == PLAIN) return env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, f, sp, stream);
+  // ---- PLAIN_MAY_REPLAY
   const int n = st->nenv, nl = c->nlayers;
   // the steady state only: a prefetched move of exactly this batch is pending, the glue has been validated by a
   // plain call, every environment moves by the same plan
@@ -776,7 +761,7 @@ int aomarl_env_step(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const f
                       (!g->sel || (c->sel_checked == g->sel && c->sel_checked_n == g->dm_dim && c->sel_checked_nm == g->nmodes)) &&
                       g->nhist >= 0 && g->nhist <= 5 && g->ring_pos >= 0 && g->ring_pos <= g->nhist &&
                       step_plan_uniform(c, n, accumx, accumy, plan);
-  if (!steady) return env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, stream);
+  if (!steady) return env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, f, sp, stream);
   hipStream_t s = (hipStream_t)stream;
   int rc = 0;
   if (pf) {
@@ -858,7 +843,7 @@ int aomarl_env_step(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const f
   };
   HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
   c->capturing = true; c->fork_recorded = false;
-  rc = env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, stream);
+  rc = env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, f, sp, stream);
   hipError_t je = hipSuccess;
   if (!rc && pf) {                                          // the side streams join the caller's stream again
     if (c->psf_side) je = hipStreamWaitEvent(s, c->ev_psf, 0);
