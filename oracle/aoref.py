@@ -68,6 +68,13 @@ def lib():
     return _lib
 
 
+def philox(ctr, key):
+    """One Philox4x32-10 block: counter (4 words), key (2 words) -> 4 words."""
+    out = np.empty(4, dtype=np.uint32)
+    lib().aoref_philox4x32_10(np.asarray(ctr, dtype=np.uint32), np.asarray(key, dtype=np.uint32), out)
+    return out
+
+
 def normals(seed, stream, counter, n):
     out = np.empty(n, dtype=np.float32)
     lib().aoref_normals(seed & 0xFFFFFFFF, stream, counter, n, out)

@@ -394,7 +394,8 @@ def _grad_views(sac, u):
 def test_native_update_matches_the_autograd_update(case):
     """aomarl_sac_update (hand-written forward + backward + Adam + soft update) against the torch
     autograd statement of the update on the same replay rows and the same normal draws: gradients of
-    the first update, then parameters, temperature and losses over several updates."""
+    the first update, then parameters, temperature and losses over several updates.
+    (The precision test of the update is tests/test_gpu_sac_update.py: float64 reference, stage by stage.)"""
     import torch
     cfg, B, n_upd = {}, 64, 4
     lay = _layout()
