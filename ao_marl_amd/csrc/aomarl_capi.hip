@@ -144,6 +144,15 @@ struct aomarl_ctx {
   float *mgain = nullptr;
   int mgain_rows = 0, mgain_nm = 0;
   std::vector<float> h_mgain;
+  // the on-line optimiser attached to this context (aomarl_modopti_online_attach) or null, and the voltage buffer of the
+  // state it was attached with: aomarl_do_control of that state feeds it and its applies write `mgain`
+  // mo_mgain_used: the gains the LAST do_control scaled with (device, the size of mgain).  aomarl_rl_control_modes
+  // recomposes that frame's command from them: an apply behind frame t must not reach back into frame t's integration.
+  // It follows `mgain` one frame late (mo_used_stale: an apply has written mgain since).
+  aomarl_modopti_online *mo = nullptr;
+  const float *mo_voltage = nullptr;
+  float *mo_mgain_used = nullptr;
+  bool mo_used_stale = false;
   uint32_t *seed_stage = nullptr;  // device staging for reset seeds
   int seed_stage_n = 0;
   // aomarl_reset_prefetch_*: the NEXT episode's screens grown in a shadow state while this episode runs
@@ -699,6 +708,8 @@ int aomarl_destroy(aomarl_ctx *c) {
   if (c->ev_psf) (void)hipEventDestroy(c->ev_psf);
   if (c->env_gain) (void)hipFree(c->env_gain);
   if (c->mgain) (void)hipFree(c->mgain);
+  if (c->mo) { mo_online_set_owner(c->mo, nullptr); c->mo = nullptr; }      // (not owned: the caller destroys it)
+  if (c->mo_mgain_used) (void)hipFree(c->mo_mgain_used);
   if (c->seed_stage) (void)hipFree(c->seed_stage);
   rp_free(c);
   if (c->timg) (void)hipFree(c->timg);
@@ -773,6 +784,9 @@ int aomarl_set_env_gains(aomarl_ctx *c, const float *gains, int nenv) {
 int aomarl_set_modal_gains(aomarl_ctx *c, const float *mgain, int nrows, int nmodes) {
   if (c) c->cfg_epoch++;
   if (!c) return fail("set_modal_gains: null ctx");
+  if (c->mo)
+    return fail("aomarl_set_modal_gains: an on-line optimiser is attached and owns the gains (aomarl_modopti_online_attach "
+                "with NULL first)");
   if (c->pipe.active)
     return fail("aomarl_set_modal_gains: a pipelined frame is in flight (aomarl_set_frame_pipeline): the frame pipeline "
                 "cannot apply or drop modal gains within an episode -- reset first");
@@ -804,7 +818,50 @@ int aomarl_get_modal_gains(aomarl_ctx *c, float *mgain_out, int *nrows_out, int 
   if (!c) return fail("get_modal_gains: null ctx");
   if (nrows_out) *nrows_out = c->mgain ? c->mgain_rows : 0;
   if (nmodes_out) *nmodes_out = c->mgain ? c->mgain_nm : 0;
+  if (mgain_out && c->mgain && c->mo) {        // the applies write the device's copy: read it back
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(c->h_mgain.data(), c->mgain, sizeof(float) * c->h_mgain.size(), hipMemcpyDeviceToHost));
+  }
   if (mgain_out && c->mgain) memcpy(mgain_out, c->h_mgain.data(), sizeof(float) * c->h_mgain.size());
+  return 0;
+}
+
+int aomarl_modopti_online_attach(aomarl_ctx *c, aomarl_state *st, aomarl_modopti_online *m) {
+  if (!c) return fail("modopti_online_attach: null ctx");
+  c->cfg_epoch++;
+  if (!m) {                          // detach: the gains stay as last applied, the host copy follows them
+    if (!c->mo) return 0;
+    if (c->mgain) {
+      HIPCHK(hipDeviceSynchronize());
+      HIPCHK(hipMemcpy(c->h_mgain.data(), c->mgain, sizeof(float) * c->h_mgain.size(), hipMemcpyDeviceToHost));
+    }
+    mo_online_set_owner(c->mo, nullptr);
+    c->mo = nullptr; c->mo_voltage = nullptr;
+    if (c->mo_mgain_used) (void)hipFree(c->mo_mgain_used);
+    c->mo_mgain_used = nullptr; c->mo_used_stale = false;
+    return 0;
+  }
+  if (!st || !st->voltage) return fail("modopti_online_attach: null state");
+  if (c->mo) return fail("modopti_online_attach: an optimiser is attached already (attach NULL first)");
+  if (mo_online_owner(m)) return fail("modopti_online_attach: this optimiser is attached to another context");
+  if (c->pipe.active)
+    return fail("modopti_online_attach: a pipelined frame is in flight (aomarl_set_frame_pipeline): reset first");
+  if (!c->mgain) return fail("modopti_online_attach: no modal gains are set (aomarl_set_modal_gains first: the applies write them)");
+  if (c->env_gain) return fail("modopti_online_attach: per-environment scalar gains are set (aomarl_set_env_gains): mgain = G / gain needs one gain");
+  if (!(c->gain > 0.f) || !isfinite(c->gain)) return fail("modopti_online_attach: gain = %g: mgain = G / gain needs a positive gain", (double)c->gain);
+  int nenv, nm, rows;
+  mo_online_dims(m, &nenv, &nm, &rows);
+  if (nm != c->nmodes || nm != c->mgain_nm) return fail("modopti_online_attach: nmodes = %d, the modal basis has %d modes, the modal gains %d", nm, c->nmodes, c->mgain_nm);
+  if (nenv != st->nenv) return fail("modopti_online_attach: nenv = %d, the state has %d environments", nenv, st->nenv);
+  if (c->mgain_rows != rows)
+    return fail("modopti_online_attach: mgain_rows = %d does not match pool (%d row%s: 1 for pooled gains, nenv otherwise)", c->mgain_rows, rows, rows == 1 ? "" : "s");
+  const size_t cnt = (size_t)c->mgain_rows * (size_t)c->mgain_nm;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMalloc((void **)&c->mo_mgain_used, sizeof(float) * cnt));
+  HIPCHK(hipMemcpy(c->mo_mgain_used, c->mgain, sizeof(float) * cnt, hipMemcpyDeviceToDevice));
+  c->mo_used_stale = false;
+  mo_online_set_owner(m, c);
+  c->mo = m; c->mo_voltage = st->voltage;
   return 0;
 }
 

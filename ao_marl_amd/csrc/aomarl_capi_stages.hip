@@ -250,6 +250,17 @@ static int do_control_modal(aomarl_ctx *c, aomarl_state *st, int b, int n, void 
                 "the slopes-to-modes matrix of these %d modes (aomarl_set_slopes2modes)", c->nmodes);
   if (c->env_gain && c->env_gain_n != st->nenv)
     return fail("do_control: %d per-environment gains set, the state has %d environments", c->env_gain_n, st->nenv);
+  // an on-line optimiser is attached with this state: it sees every frame whole.  A call with gain 0 (err alone, nothing
+  // integrated: how callers refresh err) is not a frame of the loop and does not feed it.
+  aomarl_modopti_online *mo = c->mo && c->mo_voltage == st->voltage && (c->gain != 0.f || c->env_gain) ? c->mo : nullptr;
+  if (mo) {
+    if (b != 0 || n != st->nenv)
+      return fail("do_control: an on-line modal-gain optimiser is attached (aomarl_modopti_online_attach): the partial "
+                  "environment range [%d, %d) of %d cannot feed it", b, b + n, st->nenv);
+    if (c->env_gain) return fail("do_control: an on-line modal-gain optimiser is attached: per-environment scalar gains (aomarl_set_env_gains) are not supported");
+    if (!(c->gain > 0.f)) return fail("do_control: an on-line modal-gain optimiser is attached: gain = %g must be positive", (double)c->gain);
+    if (c->pipe.active) return fail("do_control: an on-line modal-gain optimiser is attached and a pipelined frame is in flight");
+  }
   hipStream_t s = (hipStream_t)stream;
   const int na = c->sys.nactu, nsl = c->sys.nslope, nm = c->nmodes;
   Work w = work_layout(c, st->nenv);
@@ -265,6 +276,15 @@ static int do_control_modal(aomarl_ctx *c, aomarl_state *st, int b, int n, void 
   gs.fast = true; gs.sb = c->s2m_scale;
   launch_gemm_nt(gs);
   LAUNCHCHK();
+  if (mo) {                          // x = e + v2m . voltage, the pseudo-open-loop modes, before e is scaled
+    GemmArgs gp(n, nm, na, 1.0f, st->voltage, st->ld_actu, c->v2m, c->ld_v2m, 0.0f, mo_online_p(mo), nm, s);
+    gp.ws = st->work + w.GEMM; gp.ws_floats = w.gemm_floats; gp.min_chunk = 288;
+    gp.fast = true; gp.sb = c->v2m_scale;                      /* volts */
+    launch_gemm_nt(gp);
+    LAUNCHCHK();
+    rc = mo_online_pol(mo, modes, w.ldm, s);
+    if (rc) return rc;
+  }
   hipLaunchKernelGGL(k_mgain_scale, dim3((nm + 255) / 256, n), dim3(256), 0, s, modes, w.ldm, nm, c->gain, c->env_gain,
                      c->mgain, c->mgain_rows, b);
   LAUNCHCHK();
@@ -274,6 +294,17 @@ static int do_control_modal(aomarl_ctx *c, aomarl_state *st, int b, int n, void 
   gm.fast = true; gm.sa = 16.f; gm.sb = c->m2v_scale;        /* Btt coordinates x 2^4 */
   launch_gemm_nt(gm);
   LAUNCHCHK();
+  if (mo) {
+    if (c->mo_used_stale) {          // the frame behind an apply: these are now the gains the last do_control used
+      HIPCHK(hipMemcpyAsync(c->mo_mgain_used, c->mgain, sizeof(float) * (size_t)c->mgain_rows * (size_t)c->mgain_nm,
+                            hipMemcpyDeviceToDevice, s));
+      c->mo_used_stale = false;
+    }
+    bool applied = false;
+    rc = mo_online_advance(mo, c->mgain, c->gain, s, &applied);      // the bank / the apply, where the schedule says so
+    if (rc) return rc;
+    c->mo_used_stale = applied;
+  }
   return 0;
 }
 
@@ -465,7 +496,8 @@ int aomarl_rl_control_modes(aomarl_ctx *c, aomarl_state *st, int b, int n, const
   float *modes = st->work + w.MODES;
   const int na = c->sys.nactu, nm = c->nmodes;
   if (c->mgain)
-    hipLaunchKernelGGL(k_modal_compose_mgain, dim3((nm + 255) / 256, n), dim3(256), 0, s, nm, m0, m1, g, c->mgain,
+    hipLaunchKernelGGL(k_modal_compose_mgain, dim3((nm + 255) / 256, n), dim3(256), 0, s, nm, m0, m1, g,
+                       c->mo ? c->mo_mgain_used : c->mgain,      /* attached: the gains the last do_control used */
                        c->mgain_rows, b, action, c->nact, c->amode_inv, c->freedom, modes, w.ldm, modes_out);
   else
     hipLaunchKernelGGL(k_modal_compose, dim3((nm + 255) / 256, n), dim3(256), 0, s, nm, m0, m1, g, action,

@@ -38,3 +38,15 @@ AOMARL_LOCAL int gemm_batched_launch(int batch, int transA, int transB, int M, i
 AOMARL_LOCAL int gemm_g_batched(int batch, bool ak, bool bk, int M, int N, int K, const float *A, int lda, long long sA,
                                 const float *B, int ldb, long long sB, const float *bias, long long sBias, float *C, int ldc,
                                 long long sC, int relu, hipStream_t s);
+
+// the on-line modal-gain optimiser (aomarl_modopti.hip) as aomarl_do_control sees it while one is attached
+// (aomarl_modopti_online_attach, aomarl_capi_stages.hip): p = v2m . voltage goes into mo_online_p, mo_online_pol writes
+// x = e + p into the ring row of this frame, mo_online_advance counts the frame and runs the bank / the apply the
+// schedule asks for (mgain_dev: the context's modal gains, written by the apply as float(G / gain))
+struct aomarl_modopti_online;
+AOMARL_LOCAL void mo_online_dims(const aomarl_modopti_online *m, int *nenv, int *nmodes, int *rows);
+AOMARL_LOCAL const void *mo_online_owner(const aomarl_modopti_online *m);
+AOMARL_LOCAL void mo_online_set_owner(aomarl_modopti_online *m, const void *owner);
+AOMARL_LOCAL float *mo_online_p(aomarl_modopti_online *m);
+AOMARL_LOCAL int mo_online_pol(aomarl_modopti_online *m, const float *e, int lde, hipStream_t s);
+AOMARL_LOCAL int mo_online_advance(aomarl_modopti_online *m, float *mgain_dev, float gain, hipStream_t s, bool *applied);

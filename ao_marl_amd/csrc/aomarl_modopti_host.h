@@ -13,6 +13,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 #include <string>
 #include "../../include/aomarl.h"
 
@@ -63,5 +64,69 @@ static inline int mo_validate(const aomarl_modopti_desc *d, std::string &err) {
   for (int j = 0; j < d->ngain; j++)
     if (!isfinite(d->gains[j]))
       { err = mo_fmt("modopti_create: gains[%.0f] is not finite", j); return 1; }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------- on-line form
+// aomarl_modopti_online_*: the same bank fed one pseudo-open-loop frame at a time while the loop is closed.  The rules
+// below are all the host decides per frame -- no device value is read back for them.
+//   every frame:  the row enters a ring of `chunk` rows; J = forget J + e^2 for frames whose index since the last
+//                 restart is >= nskip
+//   apply:        every `period` frames (counted over all frames pushed), once at least one frame has entered J
+//   the bank kernel consumes the ring when it is full or an apply is due (and before a restart or a read-out)
+struct MoSchedule {
+  int chunk = 1;
+  long long period = 1, nskip = 0;
+  long long total = 0, since = 0, counted = 0, updates = 0;      // frames pushed; since restart; entered J; applies
+  int fill = 0;                                                  // rows waiting in the ring
+};
+struct MoAction {
+  int slot = 0;            // the ring row this frame is written to
+  int flush = 0;           // rows the bank kernel consumes behind this frame (0: none)
+  long long t0 = 0;        // ... index since restart of the first of them
+  bool apply = false;
+};
+// the frame about to be pushed: where it goes and what follows it
+static inline MoAction mo_online_step(MoSchedule &s) {
+  MoAction a;
+  a.slot = s.fill;
+  if (s.since >= s.nskip) s.counted++;
+  s.fill++; s.total++; s.since++;
+  a.apply = s.total % s.period == 0 && s.counted > 0;
+  if (s.fill == s.chunk || a.apply) { a.flush = s.fill; a.t0 = s.since - s.fill; s.fill = 0; }
+  if (a.apply) s.updates++;
+  return a;
+}
+// rows still waiting (before a restart or a read-out): consumed, the ring empty afterwards
+static inline MoAction mo_online_drain(MoSchedule &s) {
+  MoAction a;
+  a.flush = s.fill; a.t0 = s.since - s.fill; s.fill = 0;
+  return a;
+}
+// an episode reset: the filter history and the transient counter start over (the caller drains first); J, G and the
+// apply schedule go on
+static inline void mo_online_restart(MoSchedule &s) { s.since = 0; }
+
+#define MO_MAXCHUNK 32
+
+static inline int mo_online_validate(const aomarl_modopti_online_desc *d, std::string &err) {
+  if (!d) { err = "modopti_online_create: null desc"; return 1; }
+  aomarl_modopti_desc b;
+  b.nenv = d->nenv; b.nmodes = d->nmodes; b.ngain = d->ngain; b.nskip = d->nskip; b.delay = d->delay; b.gains = d->gains;
+  if (mo_validate(&b, err)) { err.replace(0, strlen("modopti_create"), "modopti_online_create"); return 1; }
+  if (d->chunk < 1 || d->chunk > MO_MAXCHUNK)
+    { err = mo_fmt("modopti_online_create: chunk = %.0f: 1..%.0f rows in the ring", d->chunk, MO_MAXCHUNK); return 1; }
+  if (d->period < 1) { err = mo_fmt("modopti_online_create: period = %.0f: at least one frame between applies", d->period); return 1; }
+  if (d->pool != 0 && d->pool != 1) { err = mo_fmt("modopti_online_create: pool = %.0f: 1 (all environments) or 0", d->pool); return 1; }
+  if (!(d->forget > 0.0 && d->forget <= 1.0)) { err = mo_fmt("modopti_online_create: forget = %g: in (0, 1]", d->forget); return 1; }
+  if (!(d->beta > 0.0 && d->beta <= 1.0)) { err = mo_fmt("modopti_online_create: beta = %g: in (0, 1]", d->beta); return 1; }
+  bool any = false;
+  for (int j = 0; j < d->ngain; j++) any = any || mo_stable((double)d->gains[j], (double)d->delay);
+  if (!any) { err = mo_fmt("modopti_online_create: no candidate gain is stable at delay = %g", d->delay); return 1; }
+  if (d->G0) {
+    const long long n = (long long)(d->pool ? 1 : d->nenv) * d->nmodes;
+    for (long long i = 0; i < n; i++)
+      if (!isfinite(d->G0[i])) { err = mo_fmt("modopti_online_create: G0[%.0f] is not finite", (double)i); return 1; }
+  }
   return 0;
 }

@@ -328,6 +328,8 @@ class VecRlSupervisor(object):
             self.autoencoder.check_range()      # a saturated fp16 launch of the last episode is an error
         self.check_range()
         self.sim.reset(self.env_seeds())
+        if getattr(self, "online_modal_gains", None) is not None:
+            self.online_modal_gains.restart()   # the filters' history starts over; J and G carry across episodes
         self._atmos_changed_behind = None
         self._rp_left = 0
         if self.reset_prefetch is not None:

@@ -176,6 +176,13 @@ SYMBOLS = [
     ("aomarl_modopti_reset", _i, [_vp]),
     ("aomarl_modopti_accumulate", _i, [_vp, _vp, _i, C.c_longlong, _vp]),
     ("aomarl_modopti_result", _i, [_vp, _vp, _vp, _ip, C.POINTER(C.c_longlong), _vp]),
+    ("aomarl_modopti_online_create", _i, [_vp, C.POINTER(C.c_void_p)]),
+    ("aomarl_modopti_online_destroy", _i, [_vp]),
+    ("aomarl_modopti_online_restart", _i, [_vp, _vp]),
+    ("aomarl_modopti_online_push", _i, [_vp, _vp, _vp]),
+    ("aomarl_modopti_online_result", _i, [_vp, _vp, _vp, _vp, _ip, C.POINTER(C.c_longlong), _vp]),
+    ("aomarl_modopti_online_last", _i, [_vp, _vp, _vp]),
+    ("aomarl_modopti_online_attach", _i, [_vp, _vp, _vp]),
     ("aomarl_psfrec_create", _i, [_vp, C.POINTER(C.c_void_p)]),
     ("aomarl_psfrec_destroy", _i, [_vp]),
     ("aomarl_psfrec_accumulate", _i, [_vp, _vp, _vp, _i, _vp]),
@@ -292,6 +299,13 @@ class RoketDesc(C.Structure):
 class ModoptiDesc(C.Structure):
     """aomarl_modopti_desc (include/aomarl.h)"""
     _fields_ = [(n, C.c_int32) for n in ("nenv", "nmodes", "ngain", "nskip")] + [("delay", C.c_float), ("gains", _fp)]
+
+
+class ModoptiOnlineDesc(C.Structure):
+    """aomarl_modopti_online_desc (include/aomarl.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("nenv", "nmodes", "ngain", "nskip", "chunk", "period", "pool")] + \
+               [("delay", C.c_float), ("forget", C.c_double), ("beta", C.c_double), ("gains", _fp),
+                ("G0", C.POINTER(C.c_double))]
 
 
 class PsfRecDesc(C.Structure):

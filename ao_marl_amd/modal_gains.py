@@ -22,7 +22,11 @@ candidate.
 `NativeLoopBank` (aomarl_modopti_*, csrc/aomarl_modopti.hip) is its restatement on the GPU.  The law the gains enter
 is VecRlSupervisor.set_modal_gains: m[t] = m[t-1] + gain * mgain[m] * e[t] in Btt coordinates.
 
+`OnlineLoopBank` / `NativeOnlineLoopBank` / `OnlineModalGains` are the same bank ON-LINE: fed in closed loop with the
+pseudo-open-loop modes x[t] = e[t] + v2m . voltage[t], with a forgetting factor, applied every `period` frames.
+
     python -m ao_marl_amd.modal_gains <config> [--nrec --gmin --gmax --ngain --envs --out gains.npz]
+    python -m ao_marl_amd.modal_gains <config> --online [--period 256 --horizon 2048 --beta 1]
 """
 import ctypes as C
 
@@ -31,7 +35,8 @@ import numpy as np
 from . import libaomarl as la
 
 __all__ = ["gain_grid", "delay_weights", "stable", "pole_radius", "argmin_gain", "LoopBank", "loop_rejection",
-           "NativeLoopBank", "record_open_loop", "ModalGainOptimizer", "optimize_modal_gains"]
+           "NativeLoopBank", "record_open_loop", "ModalGainOptimizer", "optimize_modal_gains", "OnlineLoopBank",
+           "NativeOnlineLoopBank", "OnlineModalGains"]
 
 
 def gain_grid(gmin=0.0, gmax=1.0, ngain=15):
@@ -197,20 +202,306 @@ class NativeLoopBank(object):
         return J.cpu().numpy(), arg.cpu().numpy(), st.astype(bool), int(n.value)
 
 
-def _open_loop_supervisor(sup):
+def _pool_rows(pool, nenv):
+    if pool not in ("all", None):
+        raise ValueError("pool = %r: 'all' or None" % (pool,))
+    return 1 if pool == "all" else int(nenv)
+
+
+class OnlineLoopBank(object):
+    """The float64 statement of the ON-LINE optimiser: the bank fed one pseudo-open-loop frame at a time while the loop
+    is closed, with a forgetting factor, and an apply every `period` frames.
+
+    x[t] = e[t] + p[t], e[t] = -s2m . slopes[t], p[t] = v2m . voltage[t]: the voltage apply_control applied in the
+    next_part_two of the frame whose next_part_one measured slopes[t] -- whatever produced it.  push(x [nenv][nmodes]):
+
+        eps = x - (wa c0 + wb c1 + wc c2);  c <- (c0 + g eps, c0, c1)            for every candidate g
+        if frames since restart >= nskip:  J = forget * J + eps * eps
+
+    and every `period` frames (counted over all frames pushed), once at least one frame has entered J:
+
+        Jp = J (pool=None)  or  the sum of J over the environments in ascending order (pool="all")
+        j* = argmin_gain(Jp, gains, stable);  G <- G + beta * (gains[j*] - G);  mgain(gain) = float32(G / gain)
+
+    G: [nmodes] (pooled) or [nenv][nmodes]; G0 gives its start (default zeros: the open loop).  restart() -- an episode
+    reset -- zeroes c0..c2 and the since-restart counter and keeps J and G.  With forget = 1 and no apply, J is
+    LoopBank's, bit for bit."""
+
+    def __init__(self, gains, delay, nskip=50, period=256, forget=1.0, beta=1.0, pool="all", G0=None):
+        self.gains = np.asarray(gains, dtype=np.float64).reshape(-1)
+        if self.gains.size < 1 or not np.isfinite(self.gains).all():
+            raise ValueError("gains: at least one, all finite")
+        self.w = delay_weights(delay)
+        self.delay, self.nskip, self.period = float(delay), int(nskip), int(period)
+        self.forget, self.beta, self.pool = float(forget), float(beta), pool
+        _pool_rows(pool, 1)
+        if self.nskip < 0:
+            raise ValueError("nskip = %d must not be negative" % self.nskip)
+        if self.period < 1:
+            raise ValueError("period = %d: at least one frame between applies" % self.period)
+        if not 0.0 < self.forget <= 1.0:
+            raise ValueError("forget = %r: in (0, 1]" % (forget,))
+        if not 0.0 < self.beta <= 1.0:
+            raise ValueError("beta = %r: in (0, 1]" % (beta,))
+        self.stable = stable(self.gains, self.delay)
+        if not self.stable.any():
+            raise ValueError("gains: no candidate is stable at delay %g (%s)" % (self.delay, self.gains))
+        self.G = None if G0 is None else np.array(G0, dtype=np.float64)
+        self.c = self.J = self.index = None
+        self.frames = self.since = self.counted = self.updates = 0
+
+    def restart(self):
+        if self.c is not None:
+            self.c = [np.zeros_like(self.J) for _ in range(3)]
+        self.since = 0
+
+    def push(self, x):
+        """One frame x [nenv][nmodes]; True when this frame's apply changed G."""
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim != 2:
+            raise ValueError("x must be [nenv][nmodes], got shape %s" % (x.shape,))
+        shape = x.shape + (self.gains.size,)
+        if self.J is None:
+            self.c = [np.zeros(shape) for _ in range(3)]
+            self.J = np.zeros(shape)
+            gshape = x.shape[1:] if self.pool == "all" else x.shape
+            if self.G is None:
+                self.G = np.zeros(gshape)
+            elif self.G.shape != gshape:
+                raise ValueError("G0 has shape %s, pool = %r needs %s" % (self.G.shape, self.pool, gshape))
+        elif self.J.shape != shape:
+            raise ValueError("x is %s, the bank %s" % (x.shape, self.J.shape[:-1]))
+        wa, wb, wc = self.w
+        c0, c1, c2 = self.c
+        e = x[..., None] - (wa * c0 + wb * c1 + wc * c2)
+        self.c = [c0 + self.gains * e, c0, c1]
+        if self.since >= self.nskip:
+            self.J = self.forget * self.J + e * e
+            self.counted += 1
+        self.frames += 1
+        self.since += 1
+        if self.frames % self.period == 0 and self.counted > 0:
+            self.apply()
+            return True
+        return False
+
+    def pooled(self):
+        """What the argmin sees: J, or its sum over the environments in ascending order."""
+        if self.pool != "all":
+            return self.J
+        Jp = self.J[0]
+        for e in range(1, self.J.shape[0]):
+            Jp = Jp + self.J[e]
+        return Jp
+
+    def apply(self):
+        self.index = argmin_gain(self.pooled(), self.gains, self.stable)
+        self.G = self.G + self.beta * (self.gains[self.index] - self.G)
+        self.updates += 1
+        return self.G
+
+    def mgain(self, gain):
+        """float32(G / gain): the factors on the scalar gain (a float32 on the device) that the apply writes"""
+        return (self.G / np.float64(np.float32(gain))).astype(np.float32)
+
+
+class NativeOnlineLoopBank(object):
+    """aomarl_modopti_online_* (csrc/aomarl_modopti.hip): OnlineLoopBank on the GPU, fed through push(x) -- a float32
+    device tensor [nenv][nmodes] -- or, attached to a simulator's context, by aomarl_do_control itself.  `gains` holds the
+    float32 candidates as float64, `delay` the float32 delay: what the statement has to be run with."""
+
+    def __init__(self, nenv, nmodes, gains, delay, nskip=50, period=256, forget=1.0, beta=1.0, pool="all", G0=None,
+                 chunk=32, device="cuda:0"):
+        import torch
+        self.lib = la.load()
+        self.device = torch.device(device)
+        g32 = np.ascontiguousarray(np.asarray(gains, dtype=np.float32).reshape(-1))
+        self.gains = g32.astype(np.float64)
+        self.nenv, self.nmodes, self.ngain = int(nenv), int(nmodes), int(g32.size)
+        self.rows = _pool_rows(pool, self.nenv)
+        self.pool, self.delay = pool, float(np.float32(delay))
+        self.sim = None
+        d = la.ModoptiOnlineDesc()
+        d.nenv, d.nmodes, d.ngain, d.nskip = self.nenv, self.nmodes, self.ngain, int(nskip)
+        d.chunk, d.period, d.pool, d.delay = int(chunk), int(period), 1 if pool == "all" else 0, self.delay
+        d.forget, d.beta = float(forget), float(beta)
+        d.gains = la.fptr(g32) if g32.size else None
+        g0 = None
+        if G0 is not None:
+            g0 = np.ascontiguousarray(G0, dtype=np.float64)
+            if g0.size != self.rows * self.nmodes:
+                raise ValueError("G0 has %d entries, pool = %r needs [%d][%d]" % (g0.size, pool, self.rows, self.nmodes))
+            d.G0 = g0.ctypes.data_as(C.POINTER(C.c_double))
+        self.ptr = C.c_void_p()
+        if not torch.cuda.is_available():
+            raise la.AomarlError("NativeOnlineLoopBank needs a GPU (the NumPy statement is OnlineLoopBank)")
+        with torch.cuda.device(self.device):
+            la.check(self.lib.aomarl_modopti_online_create(C.byref(d), C.byref(self.ptr)))
+
+    def __del__(self):
+        if getattr(self, "ptr", None):
+            if self.sim is not None and getattr(self.sim, "ctx", None):      # (a destroyed context has let go of it)
+                self.detach()
+            self.lib.aomarl_modopti_online_destroy(self.ptr)
+            self.ptr = None
+
+    def attach(self, sim):
+        la.check(self.lib.aomarl_modopti_online_attach(sim.ctx, C.byref(sim.st), self.ptr))
+        self.sim = sim
+
+    def detach(self):
+        if self.sim is not None:
+            la.check(self.lib.aomarl_modopti_online_attach(self.sim.ctx, C.byref(self.sim.st), None))
+            self.sim = None
+
+    def restart(self):
+        la.check(self.lib.aomarl_modopti_online_restart(self.ptr, la.raw_stream(self.device)))
+
+    def push(self, x):
+        if tuple(x.shape) != (self.nenv, self.nmodes) or str(x.dtype) != "torch.float32" or not x.is_cuda or \
+                not x.is_contiguous():
+            raise ValueError("x must be a contiguous float32 device tensor [%d][%d]" % (self.nenv, self.nmodes))
+        la.check(self.lib.aomarl_modopti_online_push(self.ptr, x.data_ptr(), la.raw_stream(self.device)))
+        return self
+
+    def last(self):
+        """The row pushed last (float32 device tensor [nenv][nmodes])."""
+        import torch
+        x = torch.empty(self.nenv, self.nmodes, dtype=torch.float32, device=self.device)
+        la.check(self.lib.aomarl_modopti_online_last(self.ptr, x.data_ptr(), la.raw_stream(self.device)))
+        return x
+
+    def result(self):
+        """(J [nenv][nmodes][ngain], index [rows][nmodes] of the last apply (-1: none yet), G [rows][nmodes], stable
+        [ngain], counts): NumPy; counts = dict(frames, since, counted, updates).  Rows waiting in the ring are consumed."""
+        import torch
+        J = torch.empty(self.nenv, self.nmodes, self.ngain, dtype=torch.float64, device=self.device)
+        arg = torch.empty(self.rows, self.nmodes, dtype=torch.int32, device=self.device)
+        G = torch.empty(self.rows, self.nmodes, dtype=torch.float64, device=self.device)
+        st = np.zeros(self.ngain, dtype=np.int32)
+        n = (C.c_longlong * 4)()
+        la.check(self.lib.aomarl_modopti_online_result(self.ptr, J.data_ptr(), arg.data_ptr(), G.data_ptr(), la.iptr(st),
+                                                       n, la.raw_stream(self.device)))
+        counts = dict(frames=int(n[0]), since=int(n[1]), counted=int(n[2]), updates=int(n[3]))
+        return J.cpu().numpy(), arg.cpu().numpy(), G.cpu().numpy(), st.astype(bool), counts
+
+
+def _open_loop_supervisor(sup, who="record_open_loop"):
     """Refuses the supervisor states in which a frame's slopes are not the ones the call order just measured."""
     sim = sup.sim
     if getattr(sup, "reset_prefetch", None) is not None:
-        raise RuntimeError("record_open_loop: a prefetched reset (reset_prefetch=%r) is not supported while recording"
-                           % (sup.reset_prefetch,))
+        raise RuntimeError("%s: a prefetched reset (reset_prefetch=%r) is not supported while recording"
+                           % (who, sup.reset_prefetch,))
     if getattr(sim, "_twin", None) is not None:
-        raise RuntimeError("record_open_loop: the frame pipeline is enabled on this simulator: slopes of odd frames "
-                           "live in its twin; switch it off behind a reset (enable_frame_pipeline(False))")
+        raise RuntimeError("%s: the frame pipeline is enabled on this simulator: slopes of odd frames "
+                           "live in its twin; switch it off behind a reset (enable_frame_pipeline(False))" % who)
     if sup.pure_delay_0:
-        raise NotImplementedError("record_open_loop: modification_online (the pure-delay-0 call order) is not covered")
+        raise NotImplementedError("%s: modification_online (the pure-delay-0 call order) is not covered" % who)
     if sup.autoencoder is not None:
-        raise NotImplementedError("record_open_loop: autoencoder: the loop model has no denoiser")
+        raise NotImplementedError("%s: autoencoder: the loop model has no denoiser" % who)
     return sup
+
+
+class OnlineModalGains(object):
+    """The integrator whose modal gains are re-optimised in closed loop: an on-line bank attached to a VecRlSupervisor.
+    gains: candidate ABSOLUTE gains (default gain_grid(); sorted, rounded to float32).  horizon: frames of memory,
+    forget = exp(-1 / horizon); None: 1 (no forgetting).  native: the device bank fed by do_control itself; False: the
+    NumPy statement fed through observe() by the caller after every next_part_one (slow: two read-backs per frame).
+
+        opt = OnlineModalGains(sup, period=256, horizon=2048).start()
+        ... run the loop; sup.reset() restarts the filters, J and G carry over ...
+        opt.G, opt.updates;  opt.stop()"""
+
+    def __init__(self, sup, gains=None, nskip=50, period=256, horizon=None, beta=1.0, pool="all", native=True, chunk=32):
+        self.sup = sup
+        g = gain_grid() if gains is None else np.asarray(gains, dtype=np.float64).reshape(-1)
+        self.gains = np.unique(g.astype(np.float32)).astype(np.float64)
+        self.nskip, self.period, self.beta, self.pool = int(nskip), int(period), float(beta), pool
+        self.native, self.chunk = bool(native), int(chunk)
+        if horizon is not None and not float(horizon) > 0.0:
+            raise ValueError("horizon = %r: a positive number of frames, or None" % (horizon,))
+        self.forget = 1.0 if horizon is None else float(np.exp(-1.0 / float(horizon)))
+        self.delay = float(np.float32(sup.s.delay))
+        self.rows = _pool_rows(pool, sup.sim.nenv)
+        self.bank = None
+
+    def start(self):
+        sup = self.sup
+        if self.bank is not None:
+            raise RuntimeError("OnlineModalGains.start: already started")
+        if getattr(sup, "online_modal_gains", None) is not None:
+            raise RuntimeError("OnlineModalGains.start: the supervisor has an on-line optimiser attached already")
+        _open_loop_supervisor(sup, "OnlineModalGains.start")
+        g = sup.gain
+        if g is None:
+            raise RuntimeError("OnlineModalGains.start: the supervisor has per-environment gains (set_gain with a vector); "
+                               "set one scalar gain first")
+        if not float(g) > 0.0:
+            raise RuntimeError("OnlineModalGains.start: the supervisor's gain is %r: no factor on it gives G" % (g,))
+        mgain = sup.modal_gains
+        if mgain is None:
+            sup.set_modal_gains(np.ones((self.rows, sup.nmodes), dtype=np.float32))
+            mgain = sup.modal_gains
+        if mgain.shape[0] != self.rows:
+            raise RuntimeError("OnlineModalGains.start: the modal gains have %d row(s), pool = %r needs %d"
+                               % (mgain.shape[0], self.pool, self.rows))
+        sup.ensure_slopes2modes()
+        G0 = np.float64(np.float32(g)) * mgain.astype(np.float64)
+        G0 = G0[0] if self.pool == "all" else G0
+        if self.native:
+            self.bank = NativeOnlineLoopBank(sup.sim.nenv, sup.nmodes, self.gains, self.delay, self.nskip, self.period,
+                                             self.forget, self.beta, self.pool, G0, chunk=self.chunk, device=sup.sim.device)
+            self.bank.attach(sup.sim)
+        else:
+            self.bank = OnlineLoopBank(self.gains, self.delay, self.nskip, self.period, self.forget, self.beta, self.pool, G0)
+        sup.online_modal_gains = self
+        return self
+
+    def observe(self):
+        """native=False only: after next_part_one, push x = slopes2modes() + volts2modes(voltage) of the frame into the
+        statement and set the gains an apply produced."""
+        if self.native:
+            raise RuntimeError("OnlineModalGains.observe: the native optimiser is fed by do_control itself")
+        sim = self.sup.sim
+        x = sim.slopes2modes().double() + sim.volts2modes(sim.voltage).double()
+        if self.bank.push(x.cpu().numpy()):
+            self.sup.sim.set_modal_gains(self.bank.mgain(self.sup.gain).reshape(self.rows, -1))
+
+    def restart(self):
+        if self.bank is not None:
+            self.bank.restart()
+
+    def stop(self):
+        if self.bank is None:
+            return
+        if self.native:
+            self.bank.detach()
+        if getattr(self.sup, "online_modal_gains", None) is self:
+            self.sup.online_modal_gains = None
+        self._final = (self.G, self.J, self.updates)
+        self.bank = None
+
+    def _read(self, k):
+        if self.bank is None:
+            final = getattr(self, "_final", None)
+            return None if final is None else final[k]
+        if self.native:
+            J, _, G, _, counts = self.bank.result()
+            return ((G[0] if self.pool == "all" else G), J, counts["updates"])[k]
+        return (self.bank.G, self.bank.J, self.bank.updates)[k]
+
+    @property
+    def G(self):
+        """The absolute gains in force: [nmodes] (pooled) or [nenv][nmodes]."""
+        return self._read(0)
+
+    @property
+    def J(self):
+        return self._read(1)
+
+    @property
+    def updates(self):
+        return self._read(2)
 
 
 def record_open_loop(sup, nrec, bank=None, chunk=64):
@@ -344,6 +635,10 @@ def main(argv=None):
     ap.add_argument("--nskip", type=int, default=50)
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--online", action="store_true", help="also run the on-line optimiser from the scalar gain")
+    ap.add_argument("--period", type=int, default=256)
+    ap.add_argument("--horizon", type=float, default=None)
+    ap.add_argument("--beta", type=float, default=1.0)
     a = ap.parse_args(argv)
     from . import params
     from .env import VecRlSupervisor
@@ -353,14 +648,26 @@ def main(argv=None):
     grid = gain_grid(s.gmin if a.gmin is None else a.gmin, s.gmax if a.gmax is None else a.gmax,
                      s.ngain if a.ngain is None else a.ngain)
     sr0 = _episode_strehl(sup, a.steps)
+    sr2 = Gon = None
+    if a.online:                          # from the scalar gain: one episode to converge in, one to be measured in
+        on = OnlineModalGains(sup, grid, nskip=a.nskip, period=a.period, horizon=a.horizon, beta=a.beta).start()
+        _episode_strehl(sup, a.steps)
+        sr2 = _episode_strehl(sup, a.steps)
+        Gon, nup = on.G, on.updates
+        on.stop()
+        sup.set_modal_gains(None)
     opt = optimize_modal_gains(sup, nrec=a.nrec, gains=grid, nskip=a.nskip)
     sr1 = _episode_strehl(sup, a.steps)
     print("scalar gain %.3f: SR LE %.4f (mean of %d environments)" % (sup.gain, float(sr0.mean()), a.envs))
     print("modal gains (min %.3f, median %.3f, max %.3f): SR LE %.4f" %
           (opt.G.min(), float(np.median(opt.G)), opt.G.max(), float(sr1.mean())))
+    if a.online:
+        print("on-line modal gains (min %.3f, median %.3f, max %.3f; %d applies, second episode): SR LE %.4f" %
+              (Gon.min(), float(np.median(Gon)), Gon.max(), nup, float(sr2.mean())))
     if a.out:
         np.savez(a.out, gains=opt.gains, G=opt.G, J=opt.J, stable=opt.stable, mgain=opt.G / sup.gain,
-                 sr_le_scalar=sr0, sr_le_modal=sr1, frames=opt.frames)
+                 sr_le_scalar=sr0, sr_le_modal=sr1, frames=opt.frames,
+                 **(dict(G_online=Gon, sr_le_online=sr2) if a.online else {}))
 
 
 if __name__ == "__main__":

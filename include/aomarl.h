@@ -716,6 +716,54 @@ int aomarl_modopti_accumulate(aomarl_modopti *m, const float *x_dev, int nframes
  * circle (g = 0, the open loop, counts as stable).  frames_out: HOST, frames accumulated so far.  Any may be NULL. */
 int aomarl_modopti_result(aomarl_modopti *m, double *J_out, int32_t *argmin_out, int32_t *stable_out,
                           long long *frames_out, void *stream);
+/* The same bank ON-LINE, in closed loop, on pseudo-open-loop modes (ao_marl_amd/modal_gains.py OnlineLoopBank is the
+ * float64 statement).  x[t] = e[t] + p[t] with e[t] = -s2m . slopes[t] and p[t] = v2m . voltage[t], the voltage
+ * aomarl_apply_control applied in the frame whose slopes these are: whatever produced it -- integrator, agents, any
+ * delay -- x is the series the mirrors-flat loop would have measured, to the modal round trip.  Per frame and candidate
+ *     e = x - (wa c0 + wb c1 + wc c2),  c <- (c0 + g e, c0, c1),  J = forget J + e^2 for frames whose index since the
+ *     last restart is >= nskip
+ * and every `period` frames (counted over all frames pushed, once a frame has entered J)
+ *     j* = argmin over the stable candidates of J (pool = 0) or of sum_env J in ascending environment order (pool = 1),
+ *     G <- G + beta (gains[j*] - G) in double,   mgain = float(G / gain) where a context is attached.
+ * One [nenv][nmodes] row per frame goes into a device ring of `chunk` rows; the bank kernel consumes it when it is full
+ * or an apply is due.  No host synchronisation, read-back or allocation per frame; no atomics; reruns, and chunk = 1
+ * against chunk = 32, give the same bits.  G0: HOST double [rows][nmodes], rows = pool ? 1 : nenv; NULL: zeros. */
+typedef struct {
+  int32_t nenv, nmodes, ngain, nskip;
+  int32_t chunk, period, pool;
+  float delay;
+  double forget, beta;
+  const float *gains;
+  const double *G0;
+} aomarl_modopti_online_desc;
+typedef struct aomarl_modopti_online aomarl_modopti_online;
+int aomarl_modopti_online_create(const aomarl_modopti_online_desc *desc, aomarl_modopti_online **out);
+/* refused while attached to a context (detach first) */
+int aomarl_modopti_online_destroy(aomarl_modopti_online *m);
+/* an episode reset: rows waiting in the ring are consumed, then c0..c2 and the since-restart counter are zeroed; J, G and
+ * the apply schedule go on.  Asynchronous on `stream`. */
+int aomarl_modopti_online_restart(aomarl_modopti_online *m, void *stream);
+/* One frame: x_dev DEVICE fp32 [nenv][nmodes] (recorded telemetry, a caller's own reconstruction ...).  An apply that falls
+ * due updates G (and the attached context's modal gains, if any).  Asynchronous on `stream`. */
+int aomarl_modopti_online_push(aomarl_modopti_online *m, const float *x_dev, void *stream);
+/* Rows waiting in the ring are consumed first.  J_out: DEVICE double [nenv][nmodes][ngain]; argmin_out: DEVICE int32
+ * [rows][nmodes], the candidate the last apply chose (-1 before the first); G_out: DEVICE double [rows][nmodes];
+ * stable_out: HOST int32 [ngain]; counts_out: HOST [4]: frames pushed, frames since the last restart, frames that entered
+ * J, applies.  Any may be NULL. */
+int aomarl_modopti_online_result(aomarl_modopti_online *m, double *J_out, int32_t *argmin_out, double *G_out,
+                                 int32_t *stable_out, long long *counts_out, void *stream);
+/* x_out: DEVICE fp32 [nenv][nmodes], the row pushed last (it stays in the ring after the bank has read it) */
+int aomarl_modopti_online_last(aomarl_modopti_online *m, float *x_out, void *stream);
+/* While attached, aomarl_do_control of the whole state `st` under modal gains forms p = v2m . st->voltage (one more
+ * product), writes x = e + p into the ring between the s2m product and the gain scaling, and behind the command update
+ * runs whatever the schedule asks for -- the bank, the apply that writes the context's DEVICE modal gains: gains derived
+ * from frames <= t act from the do_control of frame t + 1.  A call with gain 0 (err alone, nothing integrated) is not a
+ * frame of the loop and is not fed.  aomarl_get_modal_gains then returns the device's values (it
+ * synchronises); aomarl_set_modal_gains is refused.  m = NULL detaches (the gains stay as last applied) and every entry
+ * point issues the launches it issued before.  Refused: no modal gains set, or their row count not 1 (pool) / nenv (no
+ * pool); per-environment scalar gains; a gain that is not positive; a pipelined frame in flight; nenv / nmodes that do
+ * not match; and, while attached, aomarl_do_control on a partial environment range of `st`. */
+int aomarl_modopti_online_attach(aomarl_ctx *ctx, aomarl_state *st, aomarl_modopti_online *m);
 /* PSF reconstruction from the covariance of the ROKET error buffers, the Vii algorithm (guardians/gamora.py:24-100
  * psf_rec_Vii, :103-171 psf_rec_vii_cpu).  For the eigenpairs (e_k, V_k) of the modal covariance and the phase maps
  * m_k = IF^T (Btt V_k)[:-2] + TT (Btt V_k)[-2:] on the lit pixels of a p x p pupil, zero-padded to N x N (:148-159):

@@ -7,7 +7,13 @@ with float64 torch tensors on the device (one elementwise pass per frame over [n
 
 No loop is run: the series is a random walk, what the kernel costs does not depend on the values.  The torch statement
 is timed over --torch-frames frames and scaled to --frames.  Prints the time per call of aomarl_modopti_accumulate, the
-whole series, frames x series x gains per second, and the bytes of x and of filter state moved per second."""
+whole series, frames x series x gains per second, and the bytes of x and of filter state moved per second.
+
+    python tools/modopti_bench.py --online [--steps 200] [--warmup 20] [--period 256]
+
+times one frame of the general chain under modal gains (aomarl_env_step with zero actions), the on-line optimiser
+(modal_gains.OnlineModalGains) off against attached, at 10x10 / 64 environments and 40x40 / 256 environments: what the
+extra product v2m . voltage, k_mo_pol and the amortised bank and apply cost per frame."""
 import argparse
 import os
 import sys
@@ -16,6 +22,45 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def online(a):
+    """time per frame of the general chain, optimiser off / attached"""
+    import torch
+    from ao_marl_amd import modal_gains as mg
+    from ao_marl_amd import params
+    from ao_marl_amd.env import VecAoEnv
+    small = dict(n_zernike_start_end=[0, 80], n_reverse_filtered_from_cmat=5)
+    large = dict(n_zernike_start_end=[0, 1274], n_reverse_filtered_from_cmat=5, window_n_zernike=20,
+                 include_tip_tilt_windowed=True)
+    for name, nenv, rl, nag in (("production_sh_10x10_2m", 64, small, 1), ("production_sh_40x40_8m_3layers", 256, large, 13)):
+        env = VecAoEnv(params.builtin(name), nenv, rl, n_agents_modal=nag, frame_pipeline=False)
+        sup = env.supervisor
+        sup.set_modal_gains(np.ones(sup.nmodes, dtype=np.float32))
+        zero = torch.zeros(nenv, env.action_dim, device="cuda:0")
+
+        def per_frame():
+            env.reset()
+            for _ in range(a.warmup):
+                env.step(zero)
+            torch.cuda.synchronize()
+            best = 1e30
+            for _ in range(a.reps):
+                t = time.perf_counter()
+                for _ in range(a.steps):
+                    env.step(zero)
+                torch.cuda.synchronize()
+                best = min(best, (time.perf_counter() - t) / a.steps)
+            return best
+        off = per_frame()
+        opt = mg.OnlineModalGains(sup, nskip=50, period=a.period, horizon=2048, pool="all").start()
+        on = per_frame()
+        nup = opt.updates
+        opt.stop()
+        print("online  %s, %d environments, %d modes, 15 gains, period %d: %.3f ms per frame off, %.3f ms attached "
+              "(+%.3f ms, %+.1f %%; %d applies)" % (name, nenv, sup.nmodes, a.period, 1e3 * off, 1e3 * on, 1e3 * (on - off),
+                                                   100.0 * (on - off) / off, nup), flush=True)
+        del env, sup, opt
 
 
 def main(argv=None):
@@ -28,7 +73,13 @@ def main(argv=None):
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--torch-frames", type=int, default=256)
     ap.add_argument("--delay", type=float, default=1.0)
+    ap.add_argument("--online", action="store_true")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--period", type=int, default=256)
     a = ap.parse_args(argv)
+    if a.online:
+        return online(a)
     import torch
     from ao_marl_amd import modal_gains as mg
     dev = torch.device("cuda:0")
