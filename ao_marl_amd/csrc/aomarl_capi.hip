@@ -44,8 +44,6 @@ struct aomarl_ctx {
   int dft_mode = -1;                   // frame kernel DFTs: -1 follow the library's precision mode, 0 fp32 MFMAs, 1 split-fp16 ("force_f32_dft")
   bool reset_untransposed = false;     // "reset_untransposed": the reset's x extrusions on the row-major screen itself
   int small_chain = 1;                 // "small_chain": small systems run the control / agent chain of aomarl_env_step as two kernels
-  hipEvent_t ride_ev = nullptr;        // frame pipeline: the event a whole-batch one-launch move may carry on its dispatch
-  bool rode = false;                   // ... and whether it did
   int residual_shortcut = 0;           // "residual_shortcut": aomarl_env_step takes the residual modes from ONE product with v2m . cmat (aomarl_set_slopes2modes)
   int small_move = 1;                  // "small_move": 1 = one k_move_small launch per frame's move where the screens allow it
   bool small_ok = false;               // every layer has dim <= MOVE_SMALL_DIM, ns + dim <= MOVE_SMALL_K (transposed [A|B] uploaded)
@@ -60,7 +58,7 @@ struct aomarl_ctx {
   // agents / next_part_two instead of in front of the next image
   bool prefetch_atmos = false, premoved = false;
   // prefetch: the side stream has not yet waited for the frame kernel that reads the screens (ev_frame): the
-  // first kernel that WRITES them does (extrude_rounds); gather and GEMM of the first round run beside it
+  // first kernel that WRITES them does (ExtrudeRun::launch); gather and GEMM of the first round run beside it
   bool frame_wait_pending = false;
   bool screens_dirty_main = true;       // the screens / origins were last written on the caller's stream
   // power-of-two scales of the static matrices for the split-f16 GEMM (gemm_scale)
@@ -119,13 +117,12 @@ struct aomarl_ctx {
     unsigned long long steps = 0, overlapped = 0, behind = 0;
   } pipe;
   int32_t *snap_target = nullptr;        // a pipelined move: where the scatter kernels also write the origins they advance
-  bool snap_complete = false;            // ... and whether every layer of every environment group was advanced by it
   bool pipe_enabled = true;              // "frame_pipeline": 0 = plain call order although a twin is set
   bool pipe_internal = false;            // check_range: the pipelined step itself is calling
   // first write of a prefetched move: behind the OLDER frame in flight (ev_frame_prev) when the lines the move
-  // rewrites are outside the frame kernel's windows (group_overlap, decided per plan), else behind the newest
+  // rewrites are outside the frame kernel's windows (GroupPlan::overlap, decided per group), else behind the newest
   hipEvent_t ev_frame_prev = nullptr;
-  bool need_prev = false, group_overlap = false;
+  bool need_prev = false;
   bool psf_side = false;                // a k_target_finish_mfma launched on the side stream may still run
   const float *pre_screens = nullptr;
   int pre_b = 0, pre_n = 0;

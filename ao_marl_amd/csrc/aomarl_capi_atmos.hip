@@ -50,10 +50,11 @@ static int atmos_wait_pending(aomarl_ctx *c, void *stream) {
   return 0;
 }
 
-// the first kernel of a prefetched move that WRITES ring lines waits for the readers of the screens
-static int first_write_wait(aomarl_ctx *c, hipStream_t s) {
+// the first kernel of a prefetched move that WRITES ring lines waits for the readers of the screens: for the OLDER
+// frame in flight when the group's plan says the move may run beside the newest (overlap), else for the newest
+static int first_write_wait(aomarl_ctx *c, hipStream_t s, bool overlap) {
   if (s != c->atm_stream) return 0;
-  if (c->group_overlap && c->ev_frame_prev) {
+  if (overlap && c->ev_frame_prev) {
     if (c->need_prev) { HIPCHK(hipStreamWaitEvent(s, c->ev_frame_prev, 0)); c->need_prev = false; }
   } else if (c->frame_wait_pending) {
     HIPCHK(hipStreamWaitEvent(s, c->ev_frame_cur, 0));
@@ -62,31 +63,40 @@ static int first_write_wait(aomarl_ctx *c, hipStream_t s) {
   return 0;
 }
 
-// the round behind `a` as k_extrude_sg wants it; false when `b` holds a layer that `a` does not (never the case for
-// the rounds of a frame or of a reset: a layer's operations fill consecutive rounds from the first one on)
-static bool next_round(const RoundOps &a, const RoundOps &b, RoundNext &nx) {
-  nx.nops = b.nops;
-  for (int i = 0; i < AOMARL_MAX_LAYERS; i++) { nx.idx[i] = -1; nx.dir[i] = 0; nx.tflag[i] = 0; }
-  for (int j = 0; j < b.nops; j++) {
-    int at = -1;
-    for (int i = 0; i < a.nops; i++) if (a.layer[i] == b.layer[j]) at = i;
-    if (at < 0) return false;
-    nx.idx[at] = j; nx.dir[j] = b.dir[j]; nx.tflag[j] = b.tflag[j];
+// the one place that reads the move plan's facts off the context
+static AtmosFacts atmos_facts(const aomarl_ctx *c) {
+  AtmosFacts f;
+  f.nlayers = c->nlayers; f.nclass = c->nclass;
+  for (int l = 0; l < c->nlayers; l++) {
+    f.abclass[l] = c->abclass[l]; f.dim[l] = c->dim[l]; f.ns[l] = c->ns[l];
+    f.tox[l] = c->sys.layers[l].tox; f.toy[l] = c->sys.layers[l].toy;
   }
-  return b.nops > 0;
+  f.pupdiam = c->sys.pupdiam;
+  f.unfused = c->no_extrude_sg;
+  f.small = c->small_ok && c->small_move;
+  return f;
+}
+static ResetFacts reset_facts(const aomarl_ctx *c, bool whole) {
+  return ResetFacts{c->reset_streams, c->prefetch_atmos, c->capturing, whole};
 }
 
-// A sequence of extrusion rounds (round = at most one operation per layer).  Per round: stencil gather +
-// normals -> Z, Z . [A|B]^T (split-K tiles), new line -> ring.  Two consecutive rounds share a launch for the
-// scatter of the first and the gather of the second (k_extrude_sg; the second may hold fewer layers and other
-// directions): 2 launches per round instead of 3 -- every round of a reset (1296 of them) and of a frame.
-struct ExtrudeRun {          // one range of environments walking through a sequence of rounds on one stream
+// The executor of aomarl_move_plan_host.h: one range of environments walking through a sequence of rounds on one
+// stream.  Per round: stencil gather + normals -> Z, Z . [A|B]^T (split-K tiles), new line -> ring.  Two consecutive
+// rounds share a launch for the scatter of the first and the gather of the second (k_extrude_sg; the second may hold
+// fewer layers and other directions): 2 launches per round instead of 3 -- every round of a reset (1296 of them) and
+// of a frame.  Which launches a round is: round_launches; here they are launched, with the waits a record asks for.
+struct ExtrudeRun {
   aomarl_ctx *c; aomarl_state *st; int b, n; hipStream_t s; bool ordered;
-  Work w; DevState ds; float *Zb[2], *NEWL, *ZREFb[2], *WS; size_t ws_floats; bool gathered; int par;
+  Work w; DevState ds; float *Zb[2], *NEWL, *ZREFb[2], *WS; size_t ws_floats;
+  RoundCarry carry = {false, 0};
+  int nsp = 0; float pscale = 1.f;   // what the last PRODUCT left for its scatter: split-K partial tiles and their factor
   int pick_n = 0;            // > 0: the products take the tile and k split a range of pick_n environments would get
+  bool overlap = false;      // the group's verdict (first_write_wait)
+  hipEvent_t ride_ev = nullptr;      // the event a whole-batch move's last launch may carry on its dispatch ...
+  bool rode = false;                 // ... and whether it did
   // ordered = false: the caller has ordered the stream behind every reader of the screens (reset)
   ExtrudeRun(aomarl_ctx *c_, aomarl_state *st_, int b_, int n_, void *stream, bool ordered_ = true)
-      : c(c_), st(st_), b(b_), n(n_), s((hipStream_t)stream), ordered(ordered_), gathered(false), par(0) {
+      : c(c_), st(st_), b(b_), n(n_), s((hipStream_t)stream), ordered(ordered_) {
     w = work_layout(c, st->nenv);
     ds = dev_state(st);
     if (ordered) ds.origin_snap = c->snap_target;
@@ -98,77 +108,60 @@ struct ExtrudeRun {          // one range of environments walking through a sequ
     ZREFb[0] = st->work + w.ZREF + col0; ZREFb[1] = st->work + w.ZREF2 + col0;
     WS = st->work + w.GEMM_ATM + 8 * col0 * w.ldn; ws_floats = 8 * ncols * w.ldn;
   }
-  int step(const RoundOps *rounds, int r, int nrounds) {
-    // one sub-round per [A|B] class
-    for (int cls = 0; cls < c->nclass; cls++) {
-      RoundOps ops;
-      ops.nops = 0;
-      int ref = -1;
-      for (int i = 0; i < rounds[r].nops; i++)
-        if (c->abclass[rounds[r].layer[i]] == cls) {
-          ops.layer[ops.nops] = rounds[r].layer[i]; ops.dir[ops.nops] = rounds[r].dir[i];
-          ops.tflag[ops.nops] = rounds[r].tflag[i]; ops.nops++; ref = rounds[r].layer[i];
-        }
-      if (ops.nops == 0) continue;
-      const int dimc = c->dim[ref], nsc = c->ns[ref], K = dimc + nsc;
-      const int ncol = n * ops.nops;
-      // fusing across rounds only when the round is ONE sub-round (one class) and the next round repeats it
-      const bool single = ops.nops == rounds[r].nops;
-      RoundNext nx;
-      // (k_extrude_sg keeps a column's whole index list in registers: four entries per thread of its 512)
-      bool fuse_next = single && !c->no_extrude_sg && nsc <= SG_U * SG_THREADS && dimc <= SG_MAX_N && r + 1 < nrounds && next_round(rounds[r], rounds[r + 1], nx);
-      if (fuse_next)                             // (the next round must be one sub-round too: same class)
-        for (int i = 0; i < rounds[r + 1].nops; i++) fuse_next = fuse_next && c->abclass[rounds[r + 1].layer[i]] == cls;
-      float *Z = Zb[par], *ZREF = ZREFb[par];
-      if (!(gathered && single)) {
-        hipLaunchKernelGGL(k_extrude_gather, dim3(ncol, (nsc + (dimc + 3) / 4 + 255) / 256), dim3(256), 0, s, c->sys, ds, b,
-                           ops, Z, w.ldz, ZREF);
-        LAUNCHCHK();
-      }
-      GemmArgs ga(ncol, dimc, K, 1.0f, Z, w.ldz, c->sys.layers[ref].AB, c->sys.layers[ref].ldab, 0.0f, NEWL, w.ldn, s);
+  int launch(const Launch &L) {
+    const RoundOps &ops = L.ops;
+    const int ncol = n * ops.nops;
+    const int dimc = L.ref >= 0 ? c->dim[L.ref] : 0, nsc = L.ref >= 0 ? c->ns[L.ref] : 0;
+    if (L.is_write && ordered) {
+      int wrc = first_write_wait(c, s, overlap);
+      if (wrc) return wrc;
+      if (s != c->atm_stream) c->screens_dirty_main = true;
+    }
+    // (the last launch of a whole-batch move carries the caller's "moved" event on its dispatch: no marker packet
+    // of its own between the move and the frame kernel that waits for it)
+    hipEvent_t ride = (L.may_ride && ride_ev && b == 0 && n == st->nenv && !c->capturing) ? ride_ev : nullptr;
+    switch (L.kind) {
+    case GATHER:
+      hipLaunchKernelGGL(k_extrude_gather, dim3(ncol, (nsc + (dimc + 3) / 4 + 255) / 256), dim3(256), 0, s, c->sys, ds, b,
+                         ops, Zb[L.par], w.ldz, ZREFb[L.par]);
+      break;
+    case PRODUCT: {
+      GemmArgs ga(ncol, dimc, dimc + nsc, 1.0f, Zb[L.par], w.ldz, c->sys.layers[L.ref].AB, c->sys.layers[L.ref].ldab, 0.0f, NEWL, w.ldn, s);
       ga.ws = WS; ga.ws_floats = ws_floats; ga.slabs_only = true;
-      ga.fast = true; ga.sa = 256.f; ga.sb = c->ab_scale[cls];    /* split-f16: stencil values (um) and N(0,1) draws x 2^8 */
+      ga.fast = true; ga.sa = 256.f; ga.sb = c->ab_scale[L.cls];    /* split-f16: stencil values (um) and N(0,1) draws x 2^8 */
       ga.pick_M = pick_n > 0 && pick_n < n ? pick_n * ops.nops : 0;
       const GemmDone gd = launch_gemm_nt(ga);
-      const int nsp = gd.slabs;
-      const float pscale = gd.slab_alpha;
-      LAUNCHCHK();
-      if (ordered) {
-        int wrc = first_write_wait(c, s);
-        if (wrc) return wrc;
-        if (s != c->atm_stream) c->screens_dirty_main = true;
-      }
-      if (fuse_next) {
-        hipLaunchKernelGGL(k_extrude_sg, dim3(ncol), dim3(SG_THREADS), 0, s, c->sys, ds, b, ops, NEWL, w.ldn, ZREF,
-                           WS, nsp, ncol, dimc, pscale, Zb[par ^ 1], w.ldz, ZREFb[par ^ 1], nx);
-        par ^= 1;
-        gathered = true;
-      } else {
-        // (the last launch of a whole-batch move carries the caller's "moved" event on its dispatch: no marker packet
-        // of its own between the move and the frame kernel that waits for it)
-        hipEvent_t ride = (c->ride_ev && r + 1 == nrounds && cls + 1 == c->nclass && b == 0 && n == st->nenv && !c->capturing)
-                              ? c->ride_ev : nullptr;
-        hipExtLaunchKernelGGL(k_extrude_scatter, dim3(ncol), dim3(256), 0, s, nullptr, ride, 0, c->sys, ds, b, ops, NEWL, w.ldn,
-                              ZREF, WS, nsp, ncol, dimc, pscale);
-        if (ride) c->rode = true;
-        gathered = false;
-      }
-      LAUNCHCHK();
+      nsp = gd.slabs; pscale = gd.slab_alpha;
+      break;
     }
+    case SCATTER:
+      hipExtLaunchKernelGGL(k_extrude_scatter, dim3(ncol), dim3(256), 0, s, nullptr, ride, 0, c->sys, ds, b, ops, NEWL, w.ldn,
+                            ZREFb[L.par], WS, nsp, ncol, dimc, pscale);
+      break;
+    case SCATTER_GATHER:
+      hipLaunchKernelGGL(k_extrude_sg, dim3(ncol), dim3(SG_THREADS), 0, s, c->sys, ds, b, ops, NEWL, w.ldn, ZREFb[L.par],
+                         WS, nsp, ncol, dimc, pscale, Zb[L.par ^ 1], w.ldz, ZREFb[L.par ^ 1], L.next);
+      break;
+    case MOVE_SMALL:                             // small screens: the whole move of these environments in one launch
+      hipExtLaunchKernelGGL(k_move_small, dim3(n, c->nlayers), dim3(MOVE_SMALL_T), 0, s, nullptr, ride, 0, c->sys, ds, b, L.shift);
+      break;
+    }
+    LAUNCHCHK();
+    if (ride) rode = true;
+    return 0;
+  }
+  // next: the round behind `cur`, null behind the last one
+  int round(const RoundOps &cur, const RoundOps *next, const AtmosFacts &f) {
+    RoundLaunches rl;
+    round_launches(cur, next, f, carry, rl);
+    for (int i = 0; i < rl.n; i++) {
+      int rc = launch(rl.l[i]);
+      if (rc) return rc;
+    }
+    carry = rl.carry;
     return 0;
   }
 };
-
-static int extrude_rounds(aomarl_ctx *c, aomarl_state *st, int b, int n, const RoundOps *rounds, int nrounds,
-                          void *stream) {
-  if (n == 0 || nrounds == 0) return 0;
-  ExtrudeRun run(c, st, b, n, stream);
-  for (int r = 0; r < nrounds; r++) {
-    int rc = run.step(rounds, r, nrounds);
-    if (rc) return rc;
-  }
-  return 0;
-}
 
 int aomarl_extrude(aomarl_ctx *c, aomarl_state *st, int b, int n, int nops, const int32_t *layer,
                    const int32_t *dir, void *stream) {
@@ -186,73 +179,48 @@ int aomarl_extrude(aomarl_ctx *c, aomarl_state *st, int b, int n, int nops, cons
       if (layer[j] == layer[i]) return fail("extrude: a layer appears twice in one round");
     ops.layer[i] = layer[i]; ops.dir[i] = dir[i]; ops.tflag[i] = 0;
   }
-  return extrude_rounds(c, st, b, n, &ops, 1, stream);
+  return ExtrudeRun(c, st, b, n, stream).round(ops, nullptr, atmos_facts(c));
 }
 
-// plan of one env: signed pixel shifts per layer after adding the per-frame deltas
-struct Plan { int kx[AOMARL_MAX_LAYERS], ky[AOMARL_MAX_LAYERS]; };
+// what a move reports to its caller: every layer of every group moved (else somebody has to copy the origins into the
+// pipeline's snapshot), and its last launch carried ride_ev
+struct MoveDone { bool complete, rode; };
 
-static bool plan_eq(const Plan &a, const Plan &b, int nl) {
-  for (int l = 0; l < nl; l++)
-    if (a.kx[l] != b.kx[l] || a.ky[l] != b.ky[l]) return false;
-  return true;
-}
-
-static int run_plan(aomarl_ctx *c, aomarl_state *st, int b, int n, const Plan &p, void *stream) {
-  // layer l's queue: |kx| x-extrusions then |ky| y-extrusions; round r = r-th op of each layer
-  int maxr = 0;
-  for (int l = 0; l < c->nlayers; l++) {
-    int len = abs(p.kx[l]) + abs(p.ky[l]);
-    if (len > maxr) maxr = len;
-  }
-  for (int l = 0; l < c->nlayers; l++)
-    if (p.kx[l] == 0 && p.ky[l] == 0) c->snap_complete = false;   // a ring that does not move this frame: nobody writes its snapshot entry
-  if (maxr == 0) return 0;
-  if ((hipStream_t)stream != c->atm_stream || !c->atm_stream) { int rc = atmos_wait_pending(c, stream); if (rc) return rc; }
-  // frame pipeline: may this move run beside the older frame in flight?  The extrusions rewrite the |kx| oldest
-  // columns / |ky| oldest rows of each ring (logical 0.. for a positive shift, dim-1.. for a negative one):
-  // outside every window the one-pass frame kernel reads  <=>  within the margins around the pupil
-  c->group_overlap = false;
-  if (c->ev_frame_prev) {
-    bool fits = true;
-    for (int l = 0; l < c->nlayers; l++) {
-      const DevLayer &L = c->sys.layers[l];
-      const int lox = L.tox, hix = L.dim - L.tox - c->sys.pupdiam, loy = L.toy, hiy = L.dim - L.toy - c->sys.pupdiam;
-      if ((p.kx[l] > 0 ? p.kx[l] > lox : -p.kx[l] > hix) || (p.ky[l] > 0 ? p.ky[l] > loy : -p.ky[l] > hiy)) fits = false;
+// one frame's move of [b, b + n): group by group (aomarl_move_plan_host.h), each group's rounds or its one small launch
+static int move_atmos_now(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accumx, float *accumy, void *stream,
+                          hipEvent_t ride_ev, MoveDone *done) {
+  const AtmosFacts f = atmos_facts(c);
+  const int nl = f.nlayers;
+  MoveDone d = {true, false};
+  for (int e = b; e < b + n;) {
+    const MoveGroup g = move_group(nl, accumx, accumy, accumx, accumy, c->deltax, c->deltay, e, b + n);
+    if (e == b)                                  // "subpixel_flow": one remainder for the range
+      for (int l = 0; l < nl; l++) { c->frac_x[l] = g.fx[l]; c->frac_y[l] = g.fy[l]; }
+    e += g.n;
+    // frame pipeline: may this group's move run beside the older frame in flight?
+    const GroupPlan gp = group_plan(g.k, f, c->ev_frame_prev != nullptr);
+    d.complete = d.complete && gp.complete;      // a ring that does not move this frame: nobody writes its snapshot entry
+    if (gp.nrounds == 0) continue;
+    if ((hipStream_t)stream != c->atm_stream || !c->atm_stream) { int rc = atmos_wait_pending(c, stream); if (rc) return rc; }
+    if (c->ev_frame_prev) { if (gp.overlap) c->pipe.overlapped++; else c->pipe.behind++; }
+    ExtrudeRun run(c, st, g.b, g.n, stream);
+    run.overlap = gp.overlap; run.ride_ev = ride_ev;
+    int rc = 0;
+    if (gp.small) rc = run.launch(small_launch(g.k));
+    else {
+      RoundOps cur = move_round(g.k, nl, 0), next = cur;
+      for (int r = 0; r < gp.nrounds && !rc; r++, cur = next) {
+        const bool last = r + 1 == gp.nrounds;
+        if (!last) next = move_round(g.k, nl, r + 1);
+        rc = run.round(cur, last ? nullptr : &next, f);
+      }
     }
-    c->group_overlap = fits;
-    if (fits) c->pipe.overlapped++; else c->pipe.behind++;
+    if (rc) return rc;
+    d.rode = d.rode || run.rode;
   }
-  if (c->small_ok && c->small_move) {            // small screens: the whole move of these environments in one launch
-    hipStream_t s = (hipStream_t)stream;
-    MovePlan mp;
-    for (int l = 0; l < AOMARL_MAX_LAYERS; l++) { mp.kx[l] = l < c->nlayers ? p.kx[l] : 0; mp.ky[l] = l < c->nlayers ? p.ky[l] : 0; }
-    { int wrc = first_write_wait(c, s); if (wrc) return wrc; }      // it reads AND writes the rings: behind their readers
-    if (s != c->atm_stream) c->screens_dirty_main = true;
-    DevState dsm = dev_state(st);
-    dsm.origin_snap = c->snap_target;
-    // (the whole batch in this one launch: the caller's "moved" event rides on the dispatch)
-    hipEvent_t ride = (c->ride_ev && b == 0 && n == st->nenv && !c->capturing) ? c->ride_ev : nullptr;
-    hipExtLaunchKernelGGL(k_move_small, dim3(n, c->nlayers), dim3(MOVE_SMALL_T), 0, s, nullptr, ride, 0, c->sys, dsm, b, mp);
-    LAUNCHCHK();
-    if (ride) c->rode = true;
-    return 0;
-  }
-  std::vector<RoundOps> rounds((size_t)maxr);
-  for (int r = 0; r < maxr; r++) {
-    RoundOps &o = rounds[r];
-    o.nops = 0;
-    for (int l = 0; l < c->nlayers; l++) {
-      int ax = abs(p.kx[l]), ay = abs(p.ky[l]);
-      if (r < ax) { o.layer[o.nops] = l; o.dir[o.nops] = p.kx[l] > 0 ? 1 : -1; o.tflag[o.nops] = 0; o.nops++; }
-      else if (r < ax + ay) { o.layer[o.nops] = l; o.dir[o.nops] = p.ky[l] > 0 ? 2 : -2; o.tflag[o.nops] = 0; o.nops++; }
-    }
-  }
-  return extrude_rounds(c, st, b, n, rounds.data(), maxr, stream);
+  if (done) *done = d;
+  return 0;
 }
-
-static int move_atmos_now(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accumx, float *accumy,
-                          void *stream);
 
 int aomarl_move_atmos(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accumx, float *accumy,
                       void *stream) {
@@ -267,7 +235,7 @@ int aomarl_move_atmos(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accu
       return 0;
     }
   }
-  return move_atmos_now(c, st, b, n, accumx, accumy, stream);
+  return move_atmos_now(c, st, b, n, accumx, accumy, stream, nullptr, nullptr);
 }
 
 static int prefetch_atmos_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accumx, float *accumy,
@@ -284,7 +252,7 @@ static int prefetch_atmos_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, fl
   }
   // The stencil gather and the GEMM of the first round only READ the screens (like the frame kernel the
   // caller has just launched): they need not wait for it.  The first kernel that writes a ring line
-  // does (extrude_rounds).  Only in the steady state, though: if the screens were last written on the
+  // does (ExtrudeRun::launch).  Only in the steady state, though: if the screens were last written on the
   // caller's stream (reset, set_screen, an un-prefetched move), those writes are ordered before this
   // point of that stream only, so the side stream waits for it right away.
   c->side_joined = false;
@@ -298,16 +266,15 @@ static int prefetch_atmos_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, fl
   } else {
     c->frame_wait_pending = true;
   }
-  c->ride_ev = c->ev_moved; c->rode = false;
-  rc = move_atmos_now(c, st, b, n, accumx, accumy, (void *)c->atm_stream);
-  c->ride_ev = nullptr;
+  MoveDone done = {true, false};
+  rc = move_atmos_now(c, st, b, n, accumx, accumy, (void *)c->atm_stream, c->ev_moved, &done);
   if (rc) return rc;
   if (c->frame_wait_pending) {            // nothing was extruded this frame: still order the marker behind the readers
     HIPCHK(hipStreamWaitEvent(c->atm_stream, c->ev_frame_cur, 0));
     c->frame_wait_pending = false;
   }
   c->screens_dirty_main = false;
-  if (!c->rode) HIPCHK(hipEventRecord(c->ev_moved, c->atm_stream));      // (else the move's one launch carried it)
+  if (!done.rode) HIPCHK(hipEventRecord(c->ev_moved, c->atm_stream));      // (else the move's one launch carried it)
   c->premoved = true; c->pre_screens = st->screens; c->pre_b = b; c->pre_n = n;
   return 0;
 }
@@ -317,34 +284,6 @@ int aomarl_prefetch_atmos(aomarl_ctx *c, aomarl_state *st, int b, int n, float *
   return prefetch_atmos_impl(c, st, b, n, accumx, accumy, stream, false);
 }
 
-static int move_atmos_now(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accumx, float *accumy,
-                          void *stream) {
-  int rc = 0;
-  const int nl = c->nlayers;
-  int g0 = b;
-  Plan cur;
-  for (int e = b; e <= b + n; e++) {
-    Plan p;
-    if (e < b + n) {
-      for (int l = 0; l < nl; l++) {
-        float ax = accumx[(size_t)e * nl + l] + c->deltax[l];
-        float ay = accumy[(size_t)e * nl + l] + c->deltay[l];
-        int kx = (int)ax, ky = (int)ay;
-        p.kx[l] = kx; p.ky[l] = ky;
-        accumx[(size_t)e * nl + l] = ax - (float)kx;
-        accumy[(size_t)e * nl + l] = ay - (float)ky;
-        if (e == b) { c->frac_x[l] = ax - (float)kx; c->frac_y[l] = ay - (float)ky; }   // "subpixel_flow": one remainder for the range
-      }
-    }
-    if (e == b) { cur = p; continue; }
-    if (e == b + n || !plan_eq(p, cur, nl)) {
-      rc = run_plan(c, st, g0, e - g0, cur, stream);
-      if (rc) return rc;
-      g0 = e; cur = p;
-    }
-  }
-  return 0;
-}
 
 int aomarl_reset_strehl(aomarl_ctx *c, aomarl_state *st, int b, int n, void *stream) {
   int rc = check_range(c, st, b, n);
@@ -361,27 +300,18 @@ int aomarl_reset_strehl(aomarl_ctx *c, aomarl_state *st, int b, int n, void *str
 // scattered reads: one 64-byte sector each).  Done on the TRANSPOSED screen they are row
 // operations -- the x stencil with its coordinates exchanged, the zero screen is its own
 // transpose -- and one in-place transposition at the end gives the same screen, bit for bit.
-static void reset_rounds_plan(const aomarl_ctx *c, std::vector<RoundOps> &rounds) {
-  int maxr = 0;
-  for (int l = 0; l < c->nlayers; l++) if (2 * c->dim[l] > maxr) maxr = 2 * c->dim[l];
-  rounds.assign((size_t)maxr, RoundOps());
-  const bool tr = !c->reset_untransposed;
-  for (int r = 0; r < maxr; r++) {
-    RoundOps &o = rounds[r];
-    o.nops = 0;
-    for (int l = 0; l < c->nlayers; l++)
-      if (r < 2 * c->dim[l]) {
-        const int dx = c->deltax[l] > 0.f ? 1 : -1;
-        o.layer[o.nops] = l; o.dir[o.nops] = tr ? 2 * dx : dx; o.tflag[o.nops] = tr ? 1 : 0; o.nops++;
-      }
-  }
+static void reset_rounds(const aomarl_ctx *c, const AtmosFacts &f, std::vector<RoundOps> &rounds) {
+  rounds.resize((size_t)reset_nrounds(f));
+  for (size_t r = 0; r < rounds.size(); r++) rounds[r] = reset_round(f, c->deltax, !c->reset_untransposed, (int)r);
 }
-// In how many parts a reset of n environments walks its rounds (each part's products have its own columns: the
-// partition fixes the split-K order of every sum, so the prefetched reset uses the plain one's)
-static int reset_parts(const aomarl_ctx *c, int n) {
-  if (c->reset_streams > 1 && c->prefetch_atmos && n >= 16 * c->reset_streams && !c->capturing)
-    return c->reset_streams > 4 ? 4 : c->reset_streams;
-  return 1;
+// round r of every run, run by run
+static int reset_step(std::vector<ExtrudeRun> &runs, const std::vector<RoundOps> &rounds, int r, const AtmosFacts &f) {
+  const RoundOps *next = (size_t)r + 1 < rounds.size() ? &rounds[r + 1] : nullptr;
+  for (auto &run : runs) {
+    int rc = run.round(rounds[r], next, f);
+    if (rc) return rc;
+  }
+  return 0;
 }
 // the screens' last step: back from the transposed form, mirror columns
 static int reset_screens_finish(aomarl_ctx *c, aomarl_state *st, int b, int n, hipStream_t s) {
@@ -463,10 +393,13 @@ int aomarl_reset(aomarl_ctx *c, aomarl_state *st, int b, int n, const uint32_t *
   hipLaunchKernelGGL(k_fill_f32, dim3(2048), dim3(256), 0, s, st->screens + (size_t)b * c->sys.screen_stride,
                      (long long)n * c->sys.screen_stride, 0.f);
   LAUNCHCHK();
+  const AtmosFacts f = atmos_facts(c);
   std::vector<RoundOps> rounds;
-  reset_rounds_plan(c, rounds);
+  reset_rounds(c, f, rounds);
   const int maxr = (int)rounds.size();
-  const int parts = reset_parts(c, n);
+  ResetPart part[4];
+  const int parts = reset_partition(reset_facts(c, false), b, n, part);
+  std::vector<ExtrudeRun> runs;
   if (parts > 1 && side_stream(c) == 0) {
     // The batch in parts side by side, one stream each (the caller's, the extrusion stream, two more of the
     // process): a round is gather | GEMM | scatter + gather, 45 us of which 15 are latency (launch, first operand
@@ -486,26 +419,24 @@ int aomarl_reset(aomarl_ctx *c, aomarl_state *st, int b, int n, const uint32_t *
       for (int k = 0; k < 3; k++) HIPCHK(hipEventCreateWithFlags(&c->ev_reset2[k], hipEventDisableTiming));
     }
     HIPCHK(hipEventRecord(c->ev_reset, s));
-    std::vector<ExtrudeRun> runs;
-    int e0 = b;
     for (int k = 0; k < parts; k++) {
-      const int nk = (b + n - e0) / (parts - k);
       if (k) HIPCHK(hipStreamWaitEvent(str[k], c->ev_reset, 0));
-      runs.emplace_back(c, st, e0, nk, (void *)str[k], false);
-      e0 += nk;
+      runs.emplace_back(c, st, part[k].b, part[k].n, (void *)str[k], false);
     }
-    for (int r = 0; r < maxr; r++)
-      for (auto &run : runs) {
-        rc = run.step(rounds.data(), r, maxr);
-        if (rc) return rc;
-      }
+    for (int r = 0; r < maxr; r++) {
+      rc = reset_step(runs, rounds, r, f);
+      if (rc) return rc;
+    }
     for (int k = 1; k < parts; k++) {
       HIPCHK(hipEventRecord(c->ev_reset2[k - 1], str[k]));
       HIPCHK(hipStreamWaitEvent(s, c->ev_reset2[k - 1], 0));
     }
   } else {
-    rc = extrude_rounds(c, st, b, n, rounds.data(), maxr, stream);
-    if (rc) return rc;
+    runs.emplace_back(c, st, b, n, stream);
+    for (int r = 0; r < maxr; r++) {
+      rc = reset_step(runs, rounds, r, f);
+      if (rc) return rc;
+    }
   }
   rc = reset_screens_finish(c, st, b, n, s);
   if (rc) return rc;
@@ -575,22 +506,17 @@ int aomarl_reset_prefetch_begin(aomarl_ctx *c, const aomarl_state *shadow, int b
   hipLaunchKernelGGL(k_fill_f32, dim3(2048), dim3(256), 0, s, rp->shadow.screens + (size_t)b * c->sys.screen_stride,
                      (long long)n * c->sys.screen_stride, 0.f);
   LAUNCHCHK();
-  reset_rounds_plan(c, rp->rounds);
+  reset_rounds(c, atmos_facts(c), rp->rounds);
   rp->runs.clear();
-  const int parts = reset_parts(c, n);
-  if (c->reset_prefetch_whole && parts > 1 && n % parts == 0) {
-    // One range whose products take the tile and the k split of a part's (launch_gemm_nt's pick_M): every sum in the
-    // plain reset's order, so the same screens bit for bit, with half the launches beside the running episode
-    // (256 environments: the rounds alone 47 ms instead of 60, the step beside them 2.7 % shorter).
-    rp->runs.emplace_back(c, &rp->shadow, b, n, stream, false);
-    rp->runs.back().pick_n = n / parts;
-  } else {
-    int e0 = b;
-    for (int k = 0; k < parts; k++) {         // the plain reset's partition, all parts on the one stream
-      const int nk = (b + n - e0) / (parts - k);
-      rp->runs.emplace_back(c, &rp->shadow, e0, nk, stream, false);
-      e0 += nk;
-    }
+  // The plain reset's partition, all parts on the one stream -- or ("reset_prefetch_whole") one range whose products
+  // take the tile and the k split of a part's (launch_gemm_nt's pick_M): every sum in the plain reset's order, so the
+  // same screens bit for bit, with half the launches beside the running episode
+  // (256 environments: the rounds alone 47 ms instead of 60, the step beside them 2.7 % shorter).
+  ResetPart part[4];
+  const int parts = reset_partition(reset_facts(c, c->reset_prefetch_whole), b, n, part);
+  for (int k = 0; k < parts; k++) {
+    rp->runs.emplace_back(c, &rp->shadow, part[k].b, part[k].n, stream, false);
+    rp->runs.back().pick_n = part[k].pick_n;
   }
   HIPCHK(hipEventRecord(rp->ev, s));
   return 0;
@@ -605,11 +531,11 @@ int aomarl_reset_prefetch_advance(aomarl_ctx *c, int nrounds, void *stream, int 
   if (!rp->finished) {
     for (auto &run : rp->runs) run.s = s;
     const int end = nrounds < 0 ? maxr : std::min(maxr, rp->next_round + nrounds);
-    for (; rp->next_round < end; rp->next_round++)
-      for (auto &run : rp->runs) {
-        int rc = run.step(rp->rounds.data(), rp->next_round, maxr);
-        if (rc) return rc;
-      }
+    const AtmosFacts f = atmos_facts(c);
+    for (; rp->next_round < end; rp->next_round++) {
+      int rc = reset_step(rp->runs, rp->rounds, rp->next_round, f);
+      if (rc) return rc;
+    }
     if (rp->next_round >= maxr) {
       int rc = reset_screens_finish(c, &rp->shadow, rp->b, rp->n, s);
       if (rc) return rc;

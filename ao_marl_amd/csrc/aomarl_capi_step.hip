@@ -551,7 +551,7 @@ static int pipe_launch_frame(aomarl_ctx *c, aomarl_state *st, int q, void *strea
 }
 
 // the move for the frame after the newest one in flight, on the atmosphere stream: beside the newest frame when
-// the plan allows (run_plan), behind the older one in any case; then the origins that frame will use
+// the group's plan allows (GroupPlan::overlap), behind the older one in any case; then the origins that frame will use
 static int pipe_prefetch(aomarl_ctx *c, aomarl_state *st, float *accumx, float *accumy, int older, int newest) {
   auto &P = c->pipe;
   if (c->premoved) return fail("frame pipeline: a prefetched frame is already pending");
@@ -560,21 +560,20 @@ static int pipe_prefetch(aomarl_ctx *c, aomarl_state *st, float *accumx, float *
   c->ev_frame_cur = P.ev_done_cur[newest]; c->frame_wait_pending = true;
   // the kernels that advance the ring origins write them into that frame's snapshot as well (behind the same wait
   // as their ring writes); a copy of all origins only when some ring did not move at all
-  c->snap_target = P.snap[older]; c->snap_complete = true;
-  c->ride_ev = c->ev_moved; c->rode = false;
-  int rc = move_atmos_now(c, st, 0, st->nenv, accumx, accumy, (void *)c->atm_stream);
-  c->ride_ev = nullptr;
-  const bool complete = c->snap_complete;
+  c->snap_target = P.snap[older];
+  MoveDone done = {true, false};
+  int rc = move_atmos_now(c, st, 0, st->nenv, accumx, accumy, (void *)c->atm_stream, c->ev_moved, &done);
+  const bool complete = done.complete;
   c->snap_target = nullptr;
   if (!rc && !complete && c->need_prev && c->frame_wait_pending)   // nothing written yet: the copy overwrites what the older frame reads
     rc = hipStreamWaitEvent(c->atm_stream, c->ev_frame_prev, 0) == hipSuccess ? 0 : fail("frame pipeline: hipStreamWaitEvent failed");
-  c->ev_frame_prev = nullptr; c->need_prev = false; c->frame_wait_pending = false; c->group_overlap = false;
+  c->ev_frame_prev = nullptr; c->need_prev = false; c->frame_wait_pending = false;
   if (rc) return rc;
   if (!complete)
     HIPCHK(hipMemcpyAsync(P.snap[older], st->origin, sizeof(int32_t) * (size_t)st->nenv * c->nlayers * 2,
                           hipMemcpyDeviceToDevice, c->atm_stream));
   c->screens_dirty_main = false;
-  if (!(c->rode && complete)) HIPCHK(hipEventRecord(c->ev_moved, c->atm_stream));     // (else the move's one launch carried it)
+  if (!(done.rode && complete)) HIPCHK(hipEventRecord(c->ev_moved, c->atm_stream));     // (else the move's one launch carried it)
   c->premoved = true; c->pre_screens = st->screens; c->pre_b = 0; c->pre_n = st->nenv;
   return 0;
 }
@@ -693,16 +692,7 @@ int aomarl_frame_pipeline_state(aomarl_ctx *c, int *in_flight, int *consumed_in_
 // does not have (there the extrusion chain runs on beside the next step's head), which is why this mode is for
 // the launch-bound regime (small batches: 10x10 / 64 environments is host-bound at ~0.16 ms per step) and off by
 // default.  Results are identical: same kernels, same arguments, same order per stream.
-static bool step_plan_uniform(const aomarl_ctx *c, int n, const float *accumx, const float *accumy, Plan &p) {
-  const int nl = c->nlayers;
-  for (int e = 0; e < n; e++)
-    for (int l = 0; l < nl; l++) {
-      const int kx = (int)(accumx[(size_t)e * nl + l] + c->deltax[l]), ky = (int)(accumy[(size_t)e * nl + l] + c->deltay[l]);
-      if (e == 0) { p.kx[l] = kx; p.ky[l] = ky; }
-      else if (p.kx[l] != kx || p.ky[l] != ky) return false;
-    }
-  return true;
-}
+// (The extrusion plan in the key is move_uniform's, aomarl_move_plan_host.h: the function the move itself groups by.)
 
 // choose_action + env_step from C: one host round trip instead of two.  (A workgroup-per-environment kernel that ran
 // the actors as matrix-vector products inside the small systems' head launch was built and measured in round 5: 64
@@ -751,7 +741,7 @@ int aomarl_env_step(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const f
   const int n = st->nenv, nl = c->nlayers;
   // the steady state only: a prefetched move of exactly this batch is pending, the glue has been validated by a
   // plain call, every environment moves by the same plan
-  Plan plan;
+  MoveShift plan;
   // (the null stream cannot be captured: a caller on it gets the plain path)
   // (with "prefetch_atmos" off the whole step is ONE stream: a linear graph, no fork / join -- the form that replays
   // cheaply on this runtime, tools/graphbench.hip: 13 small kernels 29 us per replay against 37 us launched one by one)
@@ -760,7 +750,7 @@ int aomarl_env_step(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const f
                       (pf ? (c->premoved && c->pre_screens == st->screens && c->pre_b == 0 && c->pre_n == n) : !c->premoved) &&
                       (!g->sel || (c->sel_checked == g->sel && c->sel_checked_n == g->dm_dim && c->sel_checked_nm == g->nmodes)) &&
                       g->nhist >= 0 && g->nhist <= 5 && g->ring_pos >= 0 && g->ring_pos <= g->nhist &&
-                      step_plan_uniform(c, n, accumx, accumy, plan);
+                      move_uniform(nl, accumx, accumy, c->deltax, c->deltay, n, plan);
   if (!steady) return env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, f, sp, stream);
   hipStream_t s = (hipStream_t)stream;
   int rc = 0;
@@ -797,13 +787,10 @@ int aomarl_env_step(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const f
   if (hit) {
     HIPCHK(hipGraphLaunch(hit->exec, s));
     // the host bookkeeping the body does: wind accumulators, ring position, what is pending where
-    for (int e = 0; e < n; e++)
-      for (int l = 0; l < nl; l++) {
-        const float ax = accumx[(size_t)e * nl + l] + c->deltax[l], ay = accumy[(size_t)e * nl + l] + c->deltay[l];
-        accumx[(size_t)e * nl + l] = ax - (float)(int)ax;
-        accumy[(size_t)e * nl + l] = ay - (float)(int)ay;
-        if (e == 0) { c->frac_x[l] = ax - (float)(int)ax; c->frac_y[l] = ay - (float)(int)ay; }
-      }
+    {
+      const MoveGroup mg = move_group(nl, accumx, accumy, accumx, accumy, c->deltax, c->deltay, 0, n);     // (uniform: all n)
+      for (int l = 0; l < nl; l++) { c->frac_x[l] = mg.fx[l]; c->frac_y[l] = mg.fy[l]; }
+    }
     g->ring_pos = (g->ring_pos + 1) % (g->nhist + 1);
     if (pf) {
       c->premoved = true; c->psf_side = true; c->side_joined = true;

@@ -58,20 +58,7 @@ static const char *const g_arith_name[AR_N] = {
 // =============================================================================================
 // atmosphere: Fried-Clark extrusion on ring-buffered screens
 // =============================================================================================
-struct RoundOps {
-  int nops;
-  int layer[AOMARL_MAX_LAYERS];
-  int dir[AOMARL_MAX_LAYERS];
-  int tflag[AOMARL_MAX_LAYERS];     // 1: the screen holds the transpose (reset): dir is +-2, stencil istT
-};
-// the round behind a round, as the fused scatter + gather sees it: idx[i] = position of operation i's layer in the next
-// round (-1: that layer is done), dir / tflag of the next round's operations
-struct RoundNext {
-  int nops;
-  int idx[AOMARL_MAX_LAYERS];
-  int dir[AOMARL_MAX_LAYERS];
-  int tflag[AOMARL_MAX_LAYERS];
-};
+#include "aomarl_move_plan_host.h"    // RoundOps, RoundNext, MoveShift; SG_* and MOVE_SMALL_*: the limits the host plan tests
 
 // Z[col][0..ns) = screen[stencil] - zref ; Z[col][ns..ns+n) = amplitude * N(0,1)
 // work item j of column col, for a ring origin (ox, oy) and an extrusion counter cnt given by the caller
@@ -190,9 +177,7 @@ __global__ __launch_bounds__(256) void k_extrude_scatter(DevSys sys, DevState st
 // The next round may hold fewer layers (a frame's rounds thin out as the slower layers finish) and other
 // directions: `nx` says where this column's layer sits in it; its Z / ZREF are a second pair of buffers
 // (ZN / ZREFN: the next round numbers its columns anew, another block may still need this round's ZREF entry).
-#define SG_MAX_N 1024                            // longest line k_extrude_sg keeps in LDS (checked on the host)
-#define SG_THREADS 512                           // threads per column; SG_U stencil items per thread: ns <= SG_U * SG_THREADS
-#define SG_U 4
+// (SG_MAX_N: the longest line kept in LDS; SG_THREADS threads per column, SG_U stencil items per thread: checked on the host)
 __global__ __launch_bounds__(SG_THREADS) void k_extrude_sg(DevSys sys, DevState st, int env_begin, RoundOps ops,
                                                     const float *__restrict__ NEWL, int ldn,
                                                     const float *__restrict__ ZREF, const float *__restrict__ P,
@@ -289,14 +274,11 @@ __global__ __launch_bounds__(SG_THREADS) void k_extrude_sg(DevSys sys, DevState 
 // One block per (environment, layer): per extrusion it gathers Z = [stencil - zref | amp N(0,1)] into LDS,
 // forms the new line zref + [A|B] Z from the transposed matrix (thread = (row, K slice), coalesced over
 // rows, the K slices summed in a fixed order through LDS), writes it into the ring and goes on with the
-// origin and counter it carries in registers: |kx| x-extrusions, then |ky| y-extrusions, as run_plan
+// origin and counter it carries in registers: |kx| x-extrusions, then |ky| y-extrusions, as move_round
 // orders them.  The matrix (a few hundred KB) is re-read from L2 by every block, which is what limits
 // this to small screens: there the step is bound by the host's launches (configs[1]: 6 - 12 launches of
 // the generic rounds become 1), not by the arithmetic.  fp32 vector FMAs in both precision modes.
-constexpr int MOVE_SMALL_K = 4096, MOVE_SMALL_DIM = 256, MOVE_SMALL_T = 512;
-struct MovePlan { int kx[AOMARL_MAX_LAYERS], ky[AOMARL_MAX_LAYERS]; };
-
-__global__ __launch_bounds__(MOVE_SMALL_T) void k_move_small(DevSys sys, DevState st, int env_begin, MovePlan plan) {
+__global__ __launch_bounds__(MOVE_SMALL_T) void k_move_small(DevSys sys, DevState st, int env_begin, MoveShift plan) {
   __shared__ float Zs[MOVE_SMALL_K];
   __shared__ __attribute__((aligned(16))) float Ps[4 * MOVE_SMALL_T];     // parts x ldt partial sums
   const int e = env_begin + blockIdx.x, li = blockIdx.y, tid = threadIdx.x;

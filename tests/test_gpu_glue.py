@@ -541,16 +541,9 @@ def test_env_step_refuses_inconsistent_arguments():
     assert torch.isfinite(s2).all()
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("layers", [1, 3])
-def test_small_screen_move_in_one_launch_equals_the_generic_rounds(layers):
-    """Screens of at most 256 pixels: aomarl_move_atmos is ONE k_move_small launch (every extrusion of the
-    frame, one block per environment and layer) instead of gather / GEMM / scatter rounds.  Same Philox
-    draws, same ring writes, fp32 sums in another order: the logical screens agree to rounding after the
-    ring has wrapped, with winds of all four sign combinations and different extrusion counts per layer."""
-    import torch
+def _small_screen_system(layers):
+    """the 10x10 system with one layer, or with three layers whose winds have different speeds and all four sign combinations"""
     from ao_marl_amd import geometry as G, params, system
-    from ao_marl_amd.sim import HipSim
     ps = params.builtin("production_sh_10x10_2m")
     if layers == 3:
         a = ps.p_atmos
@@ -563,6 +556,18 @@ def test_small_screen_move_in_one_launch_equals_the_generic_rounds(layers):
         ps = ps.validate()
     s = system.from_system(G.build_system(ps))
     s.cmat = np.zeros((s.nactu, s.nslope), dtype=np.float32)
+    return s
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layers", [1, 3])
+def test_small_screen_move_in_one_launch_equals_the_generic_rounds(layers):
+    """Screens of at most 256 pixels: aomarl_move_atmos is ONE k_move_small launch (every extrusion of the
+    frame, one block per environment and layer) instead of gather / GEMM / scatter rounds.  Same Philox
+    draws, same ring writes, fp32 sums in another order: the logical screens agree to rounding after the
+    ring has wrapped, with winds of all four sign combinations and different extrusion counts per layer."""
+    from ao_marl_amd.sim import HipSim
+    s = _small_screen_system(layers)
     one, gen = HipSim(s, nenv=5), HipSim(s, nenv=5)
     gen.set_option("small_move", 0)
     seeds = [3, 1000, 77, 12345, 9]
@@ -578,6 +583,45 @@ def test_small_screen_move_in_one_launch_equals_the_generic_rounds(layers):
     # and through the step: frames formed from either atmosphere agree
     one.next_part_one(); gen.next_part_one()
     assert (one.slopes - gen.slopes).abs().max().item() < 1e-3 * gen.slopes.abs().max().item()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("small_move", [1, 0])
+def test_one_move_of_several_groups_equals_the_groups_moved_one_by_one(small_move):
+    """One aomarl_move_atmos of six environments whose accumulators make three groups -- [0, 2) moves, [2, 3) does not
+    move at all, [3, 6) takes a two-pixel step in layer 1 -- against the same start moved by three calls on exactly
+    those ranges.  A range's products see that range's columns, so every split-K sum has the same order in both: screens,
+    ring origins, extrusion counters and the returned accumulators agree bit for bit, as one k_move_small launch per
+    group ("small_move" 1) and as gather / product / scatter rounds (0)."""
+    from ao_marl_amd.sim import HipSim
+    s = _small_screen_system(3)
+    whole, parts = HipSim(s, nenv=6), HipSim(s, nenv=6)
+    seeds = [3, 1000, 77, 12345, 9, 4242]
+    groups = [(0, 2), (2, 1), (3, 3)]
+    lines = [[(1, 0), (0, 1), (1, 1)], [(0, 0), (0, 0), (0, 0)], [(0, 1), (2, 0), (1, 1)]]     # |kx|, |ky| per group and layer
+    want = np.zeros((6, 3), dtype=np.int64)
+    for sim in (whole, parts):
+        sim.set_option("small_move", small_move)
+        sim.reset(seeds)
+        for (b, n), per_layer in zip(groups, lines):
+            for layer, (mx, my) in enumerate(per_layer):
+                dx, dy, _ = sim.layer_values(layer)
+                assert dx != 0.0 and dy != 0.0
+                # accumulator + delta = +-(m + 1/2) along the wind (1/4 for no line): the shift is m lines whatever the rounding
+                sim.accumx[b:b + n, layer] = np.float32(np.sign(dx) * (mx + 0.5 if mx else 0.25)) - np.float32(dx)
+                sim.accumy[b:b + n, layer] = np.float32(np.sign(dy) * (my + 0.5 if my else 0.25)) - np.float32(dy)
+                want[b:b + n, layer] = mx + my
+    count0 = whole.t["ext_count"].clone()
+    whole.move_atmos()
+    for b, n in groups:
+        parts.move_atmos(b, n)
+    torch.cuda.synchronize()
+    assert np.array_equal((whole.t["ext_count"] - count0).cpu().numpy(), want)          # the three groups moved as laid out
+    assert torch.equal(whole.t["ext_count"], parts.t["ext_count"])
+    assert torch.equal(whole.t["origin"], parts.t["origin"])
+    assert np.array_equal(whole.accumx, parts.accumx) and np.array_equal(whole.accumy, parts.accumy)
+    for layer in range(3):
+        assert torch.equal(whole.screen(layer), parts.screen(layer)), layer
 
 
 @pytest.mark.gpu
