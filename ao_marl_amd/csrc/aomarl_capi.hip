@@ -150,6 +150,10 @@ struct aomarl_ctx {
   const float *mo_voltage = nullptr;
   float *mo_mgain_used = nullptr;
   bool mo_used_stale = false;
+  // the modal predictor attached to this context (aomarl_predictor_attach) or null, and the voltage buffer of the state it
+  // was attached with: aomarl_do_control of that state runs it in place of the integration
+  aomarl_predictor *pred = nullptr;
+  const float *pred_voltage = nullptr;
   uint32_t *seed_stage = nullptr;  // device staging for reset seeds
   int seed_stage_n = 0;
   // aomarl_reset_prefetch_*: the NEXT episode's screens grown in a shadow state while this episode runs
@@ -707,6 +711,7 @@ int aomarl_destroy(aomarl_ctx *c) {
   if (c->mgain) (void)hipFree(c->mgain);
   if (c->mo) { mo_online_set_owner(c->mo, nullptr); c->mo = nullptr; }      // (not owned: the caller destroys it)
   if (c->mo_mgain_used) (void)hipFree(c->mo_mgain_used);
+  if (c->pred) { pred_set_owner(c->pred, nullptr); c->pred = nullptr; }     // (not owned either)
   if (c->seed_stage) (void)hipFree(c->seed_stage);
   rp_free(c);
   if (c->timg) (void)hipFree(c->timg);
@@ -784,6 +789,9 @@ int aomarl_set_modal_gains(aomarl_ctx *c, const float *mgain, int nrows, int nmo
   if (c->mo)
     return fail("aomarl_set_modal_gains: an on-line optimiser is attached and owns the gains (aomarl_modopti_online_attach "
                 "with NULL first)");
+  if (c->pred && !mgain)
+    return fail("aomarl_set_modal_gains: a modal predictor is attached and modal gains are what routes every step to its "
+                "chain (aomarl_predictor_attach with NULL first)");
   if (c->pipe.active)
     return fail("aomarl_set_modal_gains: a pipelined frame is in flight (aomarl_set_frame_pipeline): the frame pipeline "
                 "cannot apply or drop modal gains within an episode -- reset first");
@@ -840,6 +848,7 @@ int aomarl_modopti_online_attach(aomarl_ctx *c, aomarl_state *st, aomarl_modopti
   }
   if (!st || !st->voltage) return fail("modopti_online_attach: null state");
   if (c->mo) return fail("modopti_online_attach: an optimiser is attached already (attach NULL first)");
+  if (c->pred) return fail("modopti_online_attach: a modal predictor is attached (aomarl_predictor_attach with NULL first): it replaces the integrator whose gains this optimises");
   if (mo_online_owner(m)) return fail("modopti_online_attach: this optimiser is attached to another context");
   if (c->pipe.active)
     return fail("modopti_online_attach: a pipelined frame is in flight (aomarl_set_frame_pipeline): reset first");
@@ -859,6 +868,31 @@ int aomarl_modopti_online_attach(aomarl_ctx *c, aomarl_state *st, aomarl_modopti
   c->mo_used_stale = false;
   mo_online_set_owner(m, c);
   c->mo = m; c->mo_voltage = st->voltage;
+  return 0;
+}
+
+int aomarl_predictor_attach(aomarl_ctx *c, aomarl_state *st, aomarl_predictor *p) {
+  if (!c) return fail("predictor_attach: null ctx");
+  c->cfg_epoch++;
+  if (!p) {                          // detach: the command stays as the last frame left it
+    if (!c->pred) return 0;
+    pred_set_owner(c->pred, nullptr);
+    c->pred = nullptr; c->pred_voltage = nullptr;
+    return 0;
+  }
+  if (!st || !st->voltage) return fail("predictor_attach: null state");
+  if (c->pred) return fail("predictor_attach: a predictor is attached already (attach NULL first)");
+  if (pred_owner(p)) return fail("predictor_attach: this predictor is attached to another context");
+  if (c->pipe.active) return fail("predictor_attach: a pipelined frame is in flight (aomarl_set_frame_pipeline): reset first");
+  if (c->mo) return fail("predictor_attach: an on-line modal-gain optimiser is attached (aomarl_modopti_online_attach with NULL first)");
+  if (!c->mgain) return fail("predictor_attach: no modal gains are set (aomarl_set_modal_gains first: they route every step to the general chain)");
+  if (c->env_gain) return fail("predictor_attach: per-environment scalar gains are set (aomarl_set_env_gains): the predictor replaces the integrator");
+  int nenv, nm;
+  pred_dims(p, &nenv, &nm);
+  if (nm != c->nmodes || nm != c->mgain_nm) return fail("predictor_attach: nmodes = %d, the modal basis has %d modes, the modal gains %d", nm, c->nmodes, c->mgain_nm);
+  if (nenv != st->nenv) return fail("predictor_attach: nenv = %d, the state has %d environments", nenv, st->nenv);
+  pred_set_owner(p, c);
+  c->pred = p; c->pred_voltage = st->voltage;
   return 0;
 }
 

@@ -261,6 +261,15 @@ static int do_control_modal(aomarl_ctx *c, aomarl_state *st, int b, int n, void 
     if (!(c->gain > 0.f)) return fail("do_control: an on-line modal-gain optimiser is attached: gain = %g must be positive", (double)c->gain);
     if (c->pipe.active) return fail("do_control: an on-line modal-gain optimiser is attached and a pipelined frame is in flight");
   }
+  // a predictor attached with this state replaces the integration; the same rule for a call with gain 0
+  aomarl_predictor *pr = c->pred && c->pred_voltage == st->voltage && (c->gain != 0.f || c->env_gain) ? c->pred : nullptr;
+  if (pr) {
+    if (b != 0 || n != st->nenv)
+      return fail("do_control: a modal predictor is attached (aomarl_predictor_attach): the partial environment range "
+                  "[%d, %d) of %d cannot feed it", b, b + n, st->nenv);
+    if (c->env_gain) return fail("do_control: a modal predictor is attached: per-environment scalar gains (aomarl_set_env_gains) are not supported");
+    if (c->pipe.active) return fail("do_control: a modal predictor is attached and a pipelined frame is in flight");
+  }
   hipStream_t s = (hipStream_t)stream;
   const int na = c->sys.nactu, nsl = c->sys.nslope, nm = c->nmodes;
   Work w = work_layout(c, st->nenv);
@@ -276,19 +285,29 @@ static int do_control_modal(aomarl_ctx *c, aomarl_state *st, int b, int n, void 
   gs.fast = true; gs.sb = c->s2m_scale;
   launch_gemm_nt(gs);
   LAUNCHCHK();
-  if (mo) {                          // x = e + v2m . voltage, the pseudo-open-loop modes, before e is scaled
-    GemmArgs gp(n, nm, na, 1.0f, st->voltage, st->ld_actu, c->v2m, c->ld_v2m, 0.0f, mo_online_p(mo), nm, s);
+  if (mo || pr) {                    // x = e + v2m . voltage, the pseudo-open-loop modes, before e is scaled
+    GemmArgs gp(n, nm, na, 1.0f, st->voltage, st->ld_actu, c->v2m, c->ld_v2m, 0.0f, mo ? mo_online_p(mo) : pred_p(pr), nm, s);
     gp.ws = st->work + w.GEMM; gp.ws_floats = w.gemm_floats; gp.min_chunk = 288;
     gp.fast = true; gp.sb = c->v2m_scale;                      /* volts */
     launch_gemm_nt(gp);
     LAUNCHCHK();
-    rc = mo_online_pol(mo, modes, w.ldm, s);
+    rc = mo ? mo_online_pol(mo, modes, w.ldm, s) : mo_pol(modes, w.ldm, pred_p(pr), n, nm, pred_x(pr), s);
     if (rc) return rc;
+  }
+  float *com = st->com + (size_t)b * st->ld_actu;
+  if (pr) {                          // c = theta . (x[t], x[t-1], ...) written over e, then com = m2v . c: nothing is integrated
+    rc = pred_frame(pr, modes, w.ldm, s);
+    if (rc) return rc;
+    GemmArgs gc(n, na, nm, 1.0f, modes, w.ldm, c->m2v, c->ld_m2v, 0.0f, com, st->ld_actu, s);
+    gc.ws = st->work + w.GEMM; gc.ws_floats = w.gemm_floats; gc.min_chunk = 288;
+    gc.fast = true; gc.sa = 16.f; gc.sb = c->m2v_scale;        /* Btt coordinates x 2^4 */
+    launch_gemm_nt(gc);
+    LAUNCHCHK();
+    return 0;
   }
   hipLaunchKernelGGL(k_mgain_scale, dim3((nm + 255) / 256, n), dim3(256), 0, s, modes, w.ldm, nm, c->gain, c->env_gain,
                      c->mgain, c->mgain_rows, b);
   LAUNCHCHK();
-  float *com = st->com + (size_t)b * st->ld_actu;
   GemmArgs gm(n, na, nm, 1.0f, modes, w.ldm, c->m2v, c->ld_m2v, 1.0f, com, st->ld_actu, s);
   gm.ws = st->work + w.GEMM; gm.ws_floats = w.gemm_floats; gm.min_chunk = 288;
   gm.fast = true; gm.sa = 16.f; gm.sb = c->m2v_scale;        /* Btt coordinates x 2^4 */
@@ -487,7 +506,9 @@ int aomarl_rl_control_modes(aomarl_ctx *c, aomarl_state *st, int b, int n, const
   int rc = check_range(c, st, b, n);
   if (rc) return rc;
   if (!c->v2m || !c->m2v) return fail("rl_control_modes: no modal basis (aomarl_set_modal)");
-  if (!m0 || !m1) return fail("rl_control_modes: null modal vectors");
+  // a predictor attached with this state: modes = c of the last frame (+ the action); m0, m1 and g are not read
+  const float *pc = c->pred && c->pred_voltage == st->voltage ? pred_c(c->pred) + (size_t)b * c->nmodes : nullptr;
+  if (!pc && (!m0 || !m1)) return fail("rl_control_modes: null modal vectors");
   if (action && c->nact <= 0) return fail("rl_control_modes: no action modes set");
   if (c->mgain && (rc = mgain_check(c, st->nenv, "rl_control_modes"))) return rc;
   if (n == 0) return 0;
@@ -495,7 +516,10 @@ int aomarl_rl_control_modes(aomarl_ctx *c, aomarl_state *st, int b, int n, const
   Work w = work_layout(c, st->nenv);
   float *modes = st->work + w.MODES;
   const int na = c->sys.nactu, nm = c->nmodes;
-  if (c->mgain)
+  if (pc)                            // k_modal_compose's expression with m0 = c and g = 0: c + 0 * c
+    hipLaunchKernelGGL(k_modal_compose, dim3((nm + 255) / 256, n), dim3(256), 0, s, nm, pc, pc, 0.f, action,
+                       c->nact, c->amode_inv, c->freedom, modes, w.ldm, modes_out);
+  else if (c->mgain)
     hipLaunchKernelGGL(k_modal_compose_mgain, dim3((nm + 255) / 256, n), dim3(256), 0, s, nm, m0, m1, g,
                        c->mo ? c->mo_mgain_used : c->mgain,      /* attached: the gains the last do_control used */
                        c->mgain_rows, b, action, c->nact, c->amode_inv, c->freedom, modes, w.ldm, modes_out);

@@ -1,6 +1,6 @@
 // aomarl_host.h -- host-side pieces shared by the translation units of libaomarl_hip.so (aomarl_capi.hip: context,
 // frame / atmosphere / control kernels and every entry point but the two below; aomarl_denoise.hip: the denoiser;
-// aomarl_denoise_train.hip: its training step (includes aomarl_gemm_g.h itself); aomarl_sac.hip: the learner's update and the grouped GEMM; aomarl_roket.hip: the ROKET filter bank; aomarl_psfrec.hip: the PSF reconstruction; aomarl_groot.hip: the GROOT covariance model; aomarl_modopti.hip: the modal-gain filter bank).  Not part of the C ABI: hidden visibility.
+// aomarl_denoise_train.hip: its training step (includes aomarl_gemm_g.h itself); aomarl_sac.hip: the learner's update and the grouped GEMM; aomarl_roket.hip: the ROKET filter bank; aomarl_psfrec.hip: the PSF reconstruction; aomarl_groot.hip: the GROOT covariance model; aomarl_modopti.hip: the modal-gain filter bank; aomarl_predictor.hip: the modal predictor).  Not part of the C ABI: hidden visibility.
 #pragma once
 #include "aomarl_dev.h"
 
@@ -50,3 +50,17 @@ AOMARL_LOCAL void mo_online_set_owner(aomarl_modopti_online *m, const void *owne
 AOMARL_LOCAL float *mo_online_p(aomarl_modopti_online *m);
 AOMARL_LOCAL int mo_online_pol(aomarl_modopti_online *m, const float *e, int lde, hipStream_t s);
 AOMARL_LOCAL int mo_online_advance(aomarl_modopti_online *m, float *mgain_dev, float gain, hipStream_t s, bool *applied);
+// k_mo_pol for any consumer of the pseudo-open-loop modes: x[nenv][nm] = e (rows lde apart) + p[nenv][nm]
+AOMARL_LOCAL int mo_pol(const float *e, int lde, const float *p, int nenv, int nm, float *x, hipStream_t s);
+
+// the modal predictor (aomarl_predictor.hip) as aomarl_do_control and aomarl_rl_control_modes see it while one is
+// attached (aomarl_predictor_attach): p = v2m . voltage goes into pred_p, x = e + p into pred_x, pred_frame runs the
+// filter on that row and writes c into pred_c ([nenv][nmodes]) and into `modes` (rows ldm apart, the GEMM operand)
+struct aomarl_predictor;
+AOMARL_LOCAL void pred_dims(const aomarl_predictor *p, int *nenv, int *nmodes);
+AOMARL_LOCAL const void *pred_owner(const aomarl_predictor *p);
+AOMARL_LOCAL void pred_set_owner(aomarl_predictor *p, const void *owner);
+AOMARL_LOCAL float *pred_p(aomarl_predictor *p);
+AOMARL_LOCAL float *pred_x(aomarl_predictor *p);
+AOMARL_LOCAL const float *pred_c(const aomarl_predictor *p);
+AOMARL_LOCAL int pred_frame(aomarl_predictor *p, float *modes, int ldm, hipStream_t s);

@@ -338,10 +338,14 @@ void mo_online_set_owner(aomarl_modopti_online *m, const void *owner) { m->owner
 float *mo_online_p(aomarl_modopti_online *m) { return m->p; }
 static float *mo_online_slot(aomarl_modopti_online *m) { return m->ring + (size_t)m->sch.fill * (size_t)m->nseries; }
 
-int mo_online_pol(aomarl_modopti_online *m, const float *e, int lde, hipStream_t s) {
-  hipLaunchKernelGGL(k_mo_pol, dim3((m->nmodes + 255) / 256, m->nenv), dim3(256), 0, s, e, lde, m->p, m->nmodes, mo_online_slot(m));
+int mo_pol(const float *e, int lde, const float *p, int nenv, int nm, float *x, hipStream_t s) {
+  hipLaunchKernelGGL(k_mo_pol, dim3((nm + 255) / 256, nenv), dim3(256), 0, s, e, lde, p, nm, x);
   LAUNCHCHK();
   return 0;
+}
+
+int mo_online_pol(aomarl_modopti_online *m, const float *e, int lde, hipStream_t s) {
+  return mo_pol(e, lde, m->p, m->nenv, m->nmodes, mo_online_slot(m), s);
 }
 
 // the frame just written into mo_online_slot is counted; the bank and the apply follow where the schedule says so

@@ -330,6 +330,8 @@ class VecRlSupervisor(object):
         self.sim.reset(self.env_seeds())
         if getattr(self, "online_modal_gains", None) is not None:
             self.online_modal_gains.restart()   # the filters' history starts over; J and G carry across episodes
+        if getattr(self, "modal_predictor", None) is not None:
+            self.modal_predictor.restart()      # the predictors' history starts over; theta and P carry across episodes
         self._atmos_changed_behind = None
         self._rp_left = 0
         if self.reset_prefetch is not None:
@@ -473,6 +475,8 @@ class VecRlSupervisor(object):
         self._check_atmos_change()
         self.materialize_control()              # a frame still waiting for its do_control
         self._err_stale = False
+        if defer_control and getattr(self, "modal_predictor", None) is not None:
+            defer_control = False               # the predictor is run by do_control: every frame has to reach it
         if defer_control and do_control:
             do_control = False
             self._control_pending = True

@@ -183,6 +183,15 @@ SYMBOLS = [
     ("aomarl_modopti_online_result", _i, [_vp, _vp, _vp, _vp, _ip, C.POINTER(C.c_longlong), _vp]),
     ("aomarl_modopti_online_last", _i, [_vp, _vp, _vp]),
     ("aomarl_modopti_online_attach", _i, [_vp, _vp, _vp]),
+    ("aomarl_predictor_create", _i, [_vp, C.POINTER(C.c_void_p)]),
+    ("aomarl_predictor_destroy", _i, [_vp]),
+    ("aomarl_predictor_restart", _i, [_vp, _vp]),
+    ("aomarl_predictor_set_learning", _i, [_vp, _i]),
+    ("aomarl_predictor_push", _i, [_vp, _vp, _i, C.c_longlong, _vp, _vp]),
+    ("aomarl_predictor_get", _i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_longlong), _vp]),
+    ("aomarl_predictor_set", _i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("aomarl_predictor_last", _i, [_vp, _vp, _vp, _vp]),
+    ("aomarl_predictor_attach", _i, [_vp, _vp, _vp]),
     ("aomarl_psfrec_create", _i, [_vp, C.POINTER(C.c_void_p)]),
     ("aomarl_psfrec_destroy", _i, [_vp]),
     ("aomarl_psfrec_accumulate", _i, [_vp, _vp, _vp, _i, _vp]),
@@ -306,6 +315,12 @@ class ModoptiOnlineDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("nenv", "nmodes", "ngain", "nskip", "chunk", "period", "pool")] + \
                [("delay", C.c_float), ("forget", C.c_double), ("beta", C.c_double), ("gains", _fp),
                 ("G0", C.POINTER(C.c_double))]
+
+
+class PredictorDesc(C.Structure):
+    """aomarl_predictor_desc (include/aomarl.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("nenv", "nmodes", "order", "nskip")] + \
+               [("delay", C.c_float), ("forget", C.c_double), ("p0", C.c_double)]
 
 
 class PsfRecDesc(C.Structure):

@@ -431,6 +431,9 @@ class OnlineModalGains(object):
             raise RuntimeError("OnlineModalGains.start: already started")
         if getattr(sup, "online_modal_gains", None) is not None:
             raise RuntimeError("OnlineModalGains.start: the supervisor has an on-line optimiser attached already")
+        if getattr(sup, "modal_predictor", None) is not None:
+            raise RuntimeError("OnlineModalGains.start: a modal predictor is attached (predictive.ModalPredictor.stop "
+                               "first): it replaces the integrator whose gains this optimises")
         _open_loop_supervisor(sup, "OnlineModalGains.start")
         g = sup.gain
         if g is None:

@@ -764,6 +764,55 @@ int aomarl_modopti_online_last(aomarl_modopti_online *m, float *x_out, void *str
  * pool); per-environment scalar gains; a gain that is not positive; a pipelined frame in flight; nenv / nmodes that do
  * not match; and, while attached, aomarl_do_control on a partial environment range of `st`. */
 int aomarl_modopti_online_attach(aomarl_ctx *ctx, aomarl_state *st, aomarl_modopti_online *m);
+/* Modal PREDICTIVE control: one recursive-least-squares predictor per (environment, Btt mode) on the pseudo-open-loop
+ * modes x[t] = e[t] + p[t] above (ao_marl_amd/predictive.py PredictorBank is the float64 statement;
+ * csrc/aomarl_predictor_fn.h the update).  With h[s] = (x[s], ..., x[s-order+1]), zero before the last restart, and f the
+ * frames since it:
+ *     phi = wa h[t-1] + wb h[t-2] + wc h[t-3];   eps = x[t] - theta . phi
+ *     f >= nskip:               J = forget J + eps^2,  J0 = forget J0 + x[t]^2
+ *     learning, f >= order + 2: q = P phi, den = forget + phi . q, theta += q eps / den, P = (P - q q^T / den) / forget,
+ *                               and P *= order p0 / trace(P) where the trace exceeds order p0
+ *     c[t] = theta . h[t]       (theta after the update; rounded once to fp32)
+ * from theta = (1, 0, ...), P = p0 I.  One lane per series, double throughout, the state in registers for all the frames
+ * of a call; no atomics, no reduction: reruns and any split of the frames over calls give the same bits.  No host
+ * synchronisation, read-back or allocation per frame. */
+typedef struct {
+  int32_t nenv, nmodes, order, nskip;      /* order 1..8 */
+  float delay;                             /* 0..2, as aomarl_apply_control's */
+  double forget, p0;                       /* forget in (0, 1]; p0 > 0, in units of 1 / x^2 */
+} aomarl_predictor_desc;
+typedef struct aomarl_predictor aomarl_predictor;
+int aomarl_predictor_create(const aomarl_predictor_desc *desc, aomarl_predictor **out);
+/* refused while attached to a context (detach first) */
+int aomarl_predictor_destroy(aomarl_predictor *p);
+/* an episode reset: the past values and the since-restart counter are zeroed; theta, P, J, J0 carry over.  Asynchronous. */
+int aomarl_predictor_restart(aomarl_predictor *p, void *stream);
+/* on != 0: theta and P are updated (the default); 0: frozen -- c, J and J0 go on */
+int aomarl_predictor_set_learning(aomarl_predictor *p, int on);
+/* nframes rows of recorded telemetry: x_dev DEVICE fp32, row t at x_dev + t * frame_stride, each [nenv][nmodes];
+ * c_out_dev DEVICE fp32 [nframes][nenv][nmodes] or NULL.  One launch; the state is loaded once.  Refused while attached. */
+int aomarl_predictor_push(aomarl_predictor *p, const float *x_dev, int nframes, long long frame_stride, float *c_out_dev,
+                          void *stream);
+/* theta_out: DEVICE double [nenv][nmodes][order]; P_out: DEVICE double [nenv][nmodes][order][order] (full, symmetric);
+ * J_out, J0_out: DEVICE double [nenv][nmodes]; counts_out: HOST [3]: frames pushed, frames since the last restart, frames
+ * that updated theta.  Any may be NULL. */
+int aomarl_predictor_get(aomarl_predictor *p, double *theta_out, double *P_out, double *J_out, double *J0_out,
+                         long long *counts_out, void *stream);
+/* theta, P: HOST doubles in aomarl_predictor_get's layouts (checkpoints, warm starts); either may be NULL.  P must be
+ * symmetric with a positive diagonal.  Synchronises. */
+int aomarl_predictor_set(aomarl_predictor *p, const double *theta, const double *P);
+/* x_out, c_out: DEVICE fp32 [nenv][nmodes]: the row consumed last and the command modes it gave.  Either may be NULL. */
+int aomarl_predictor_last(aomarl_predictor *p, float *x_out, float *c_out, void *stream);
+/* While attached, aomarl_do_control of the whole state `st` forms err as ever, e = -s2m . slopes, p = v2m . st->voltage and
+ * x = e + p, runs the predictor on x (one launch) and sets com = m2v . c in place of the integration; and
+ * aomarl_rl_control_modes composes modes = c (+ action * freedom on the action modes): m0, m1 and g are accepted and
+ * ignored.  A call with gain 0 (err alone) is not a frame of the loop and is not fed.  p = NULL detaches, and every entry
+ * point issues the launches it issued before.  Refused: no modal gains set (they route every step to the general
+ * chain; their values are not used while attached, and aomarl_set_modal_gains(NULL) is refused); an on-line gain
+ * optimiser attached (aomarl_modopti_online_attach refuses a context with a predictor likewise); per-environment
+ * scalar gains; a pipelined frame in flight; nenv / nmodes that do not match; and, while attached, aomarl_do_control on
+ * a partial environment range of `st`. */
+int aomarl_predictor_attach(aomarl_ctx *ctx, aomarl_state *st, aomarl_predictor *p);
 /* PSF reconstruction from the covariance of the ROKET error buffers, the Vii algorithm (guardians/gamora.py:24-100
  * psf_rec_Vii, :103-171 psf_rec_vii_cpu).  For the eigenpairs (e_k, V_k) of the modal covariance and the phase maps
  * m_k = IF^T (Btt V_k)[:-2] + TT (Btt V_k)[-2:] on the lit pixels of a p x p pupil, zero-padded to N x N (:148-159):
