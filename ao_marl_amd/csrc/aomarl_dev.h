@@ -180,6 +180,45 @@ __device__ __forceinline__ float philox_normal(uint32_t seed, uint32_t stream, u
   return (idx & 1) ? r * sinf(a) : r * cosf(a);
 }
 
+__device__ __forceinline__ float poisson_draw(float lam, float u, float zn) {
+  if (!(lam > 0.f)) return 0.f;
+  if (lam < 30.f) {
+    // hardware exp2 / reciprocal (1 ulp): the cumulative sums move in their last bit against the
+    // oracle's libm, which flips a count where u sits within ~1e-7 of a threshold
+    float p = __expf(-lam), c = p;
+    int k = 0;
+    // the fp32 cumulative sum levels off a few ulps below 1 (0.9999999 for lam = 1) while u01 reaches 1.0: for a u
+    // above that level `u > c` never fails and the count would run to the cap (200 photons in a dark pixel, ~1e-7 of
+    // the pixels, at different u on the two sides).  Stop where the sum stops growing: the count there is the tail's end
+    while (u > c && k < 200) {
+      k++;
+      p *= lam * __builtin_amdgcn_rcpf((float)k);
+      const float cn = c + p;
+      if (cn == c) break;
+      c = cn;
+    }
+    return (float)k;
+  }
+  float v = floorf(lam + sqrtf(lam) * zn + 0.5f);
+  return v < 0.f ? 0.f : v;
+}
+
+// photon + read noise of one pixel: ONE Philox block per (pixel, frame) -- word 0: uniform of the
+// Poisson inversion, words 1, 2: a Box-Muller pair (cosine branch: rounded-normal Poisson for
+// lam >= 30, sine branch: read noise).  Same rule as oracle/aoref.c:aoref_sh_noise.
+__device__ __forceinline__ float sh_noise(float lam, float sigma, uint32_t seed, uint32_t frame, uint32_t idx) {
+  uint32_t x[4];
+  philox4x32_10(idx, frame, 0u, 4u, seed, 0x414F4D52u, x);
+  // Box-Muller on the transcendental unit: log2, and sin / cos of an angle given in revolutions
+  // (v_sin_f32 / v_cos_f32 take exactly that) -- ~6 instructions against ~150 for libm's logf, sinf,
+  // cosf; the normals agree with the oracle's to ~1e-6
+  const float r = sqrtf(-2.0f * __logf(u01(x[1])));
+  const float t = u01(x[2]);
+  float v = poisson_draw(lam, u01(x[0]), r * __builtin_amdgcn_cosf(t));
+  if (sigma > 0.f) v += sigma * (r * __builtin_amdgcn_sinf(t));
+  return v;
+}
+
 // ring-buffered screen: logical (x, y) -> physical float index.  Physical rows are
 // n + RING_PAD floats long: columns [n, n + RING_PAD) mirror columns [0, RING_PAD), so up to
 // RING_PAD consecutive logical pixels starting at a physical column < n are consecutive floats:

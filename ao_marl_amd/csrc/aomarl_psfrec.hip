@@ -12,7 +12,7 @@
 //                non-zero rows, N-point transforms in LDS, acc += w_k |.|^2 in registers over the modes of the batch.
 //                One thread owns its elements of acc and adds the modes in order: no atomics, same bits however the
 //                modes are split into calls and batches.
-// The transform (pr_fft_lds) is an in-place radix-2 decimation-in-frequency pass over lines held in LDS: natural order
+// The transform (pr_fft_lds, aomarl_fft_lds.h) is an in-place radix-2 decimation-in-frequency pass over lines held in LDS: natural order
 // in, bit-reversed order out, twiddles from a table.  Nothing is ever un-scrambled on the hot path: the row pass keeps
 // its columns, and the column pass its rows, in LDS position order (T's column c holds frequency brev(2c), column N/2
 // frequency N/2; acc's row q holds frequency brev(q)); the split of the packed rows pairs position q with
@@ -25,6 +25,7 @@
 // transposed, un-scrambled store; two of them make a 2-D transform.
 #include "aomarl_host.h"
 #include "aomarl_psfrec_host.h"
+#include "aomarl_fft_lds.h"
 #include <math.h>
 #include <string.h>
 
@@ -33,34 +34,6 @@
 // bytes of T and maps a batch of modes may occupy: well inside the 256 MB last-level cache, so that the row pass's
 // output is still there when the column pass reads it
 #define PR_BATCH_BYTES (96ll << 20)
-
-template <int CW> __device__ __forceinline__ int pr_sw(int i) {
-  constexpr int G = 32 / CW;
-  return i ^ ((i & G) ? (G - 1) : 0);
-}
-__device__ __forceinline__ int pr_brev(int q, int logn) { return (int)(__brev((unsigned)q) >> (32 - logn)); }
-
-// x: CW lines of N = 2^logn points, laid out as above, written and synchronised by the caller.  Leaves X[brev(q)] of
-// line c at slot pr_sw(q) * CW + c, synchronised.  tw[j] = exp(-2 pi i j / N), j < N / 2.
-template <int CW>
-__device__ __forceinline__ void pr_fft_lds(float2 *x, int logn, const float2 *__restrict__ tw, bool inv, int tid, int nthreads) {
-  const int nbf = (1 << (logn - 1)) * CW;
-  for (int ls = logn - 1; ls >= 0; ls--) {
-    const int s = 1 << ls;
-    for (int bf = tid; bf < nbf; bf += nthreads) {
-      const int j = bf / CW, c = bf - j * CW;
-      const int r = j & (s - 1), i = ((j >> ls) << (ls + 1)) + r;
-      float2 w = tw[r << (logn - 1 - ls)];
-      if (inv) w.y = -w.y;
-      const int ia = pr_sw<CW>(i) * CW + c, ib = pr_sw<CW>(i + s) * CW + c;
-      const float2 a = x[ia], b = x[ib];
-      const float dx = a.x - b.x, dy = a.y - b.y;
-      x[ia] = make_float2(a.x + b.x, a.y + b.y);
-      x[ib] = make_float2(dx * w.x - dy * w.y, dx * w.y + dy * w.x);
-    }
-    __syncthreads();
-  }
-}
 
 // --------------------------------------------------------------------------------------------------- per mode
 // maps [nb][p][p] (only lit pixels are ever written, the rest stays zero), var [npts]

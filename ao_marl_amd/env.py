@@ -477,10 +477,23 @@ class VecRlSupervisor(object):
         self._err_stale = False
         if defer_control and getattr(self, "modal_predictor", None) is not None:
             defer_control = False               # the predictor is run by do_control: every frame has to reach it
+        if self.pyramid is not None:
+            defer_control = False               # err comes from the pyramid's own product: nothing to run on demand
         if defer_control and do_control:
             do_control = False
             self._control_pending = True
-        if self.autoencoder is not None:
+        if self.pyramid is not None:
+            # a pyramid.PyramidSensor is attached: the same frame with its measurement in place of the Shack-Hartmann's
+            # (move, target PSF, the sensor's pupil phase, image and slopes, err = -cmat_pyr . slopes, com += gain err)
+            self._move_or_keep(move_atmos)
+            self.sim.target_psf()
+            self.sim.raytrace_wfs(atm=True, dms=True, reset=True)
+            if self.prefetch_atmos and move_atmos:
+                self.sim.prefetch_atmos()
+            self.pyramid.measure()
+            if do_control:
+                self.pyramid.control()
+        elif self.autoencoder is not None:
             # rlSupervisor.py:975-984 with the denoiser between image formation and centroiding;
             # the bincube never leaves the device (the reference copies it to the host and back)
             self._move_or_keep(move_atmos)
@@ -562,7 +575,12 @@ class VecRlSupervisor(object):
     def _get_command0(self):
         return self.sim.com
 
+    # a pyramid.PyramidSensor between its start() and stop(), or None
+    pyramid = None
+
     def get_slopes(self):
+        if self.pyramid is not None:
+            return self.pyramid.slopes
         return self.sim.slopes
 
     def get_err(self):
@@ -1081,7 +1099,7 @@ class VecAoEnv(object):
             sup.sim.volts2modes(sup.get_command(), out=self._ring[nxt])
         self._ring_pos = nxt
         if (self.residual_shortcut and self.modal_shortcut and sup.geo is None and sup.gain is not None
-                and sup.autoencoder is None and hasattr(sup.sim, "slopes2modes")):
+                and sup.autoencoder is None and sup.pyramid is None and hasattr(sup.sim, "slopes2modes")):
             # the next control step rebuilds the command from Btt coordinates (rl_step below), so
             # the frame needs neither err nor the integrated command in actuator space: one product
             # with v2m . cmat instead of do_control + volts2modes; do_control runs on demand
@@ -1104,6 +1122,7 @@ class VecAoEnv(object):
         sup = self.supervisor
         return (self.native_step and self._native_glue and self._default_state_layout and
                 self.modal_shortcut and self._modal_valid and not linear_control and
+                sup.pyramid is None and                       # (a pyramid runs the call-by-call path)
                 sup.geo is None and sup.gain is not None and not sup.pure_delay_0 and
                 not sup.keep_wfs_phase and not sup.keep_tar_image and not sup.keep_le_image and       # (the frame's sensor phase is snapped behind the Python next_part_one)
                 sup.freedom_vector is not None and not sup.next_part_one_split and
@@ -1309,7 +1328,7 @@ class VecAoEnv(object):
         it away (train_rpc.py:641); it is only evaluated here on request."""
         pair, out = None, None
         if (self.modal_shortcut and self._native_glue and self._default_state_layout and
-                self._modal_valid and not linear_control):
+                self._modal_valid and not linear_control and self.supervisor.pyramid is None):
             pair = (self._ring_slot(0), self._res_modes)
             out = self._ring_slot(-1)           # the slot the next linear_step makes the newest
         self.supervisor.next_part_two(action, linear_control=linear_control,

@@ -197,6 +197,11 @@ SYMBOLS = [
     ("aomarl_psfrec_accumulate", _i, [_vp, _vp, _vp, _i, _vp]),
     ("aomarl_psfrec_finish", _i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     ("aomarl_psfrec_reset", _i, [_vp]),
+    ("aomarl_pyr_create", _i, [_vp, C.POINTER(C.c_void_p)]),
+    ("aomarl_pyr_destroy", _i, [_vp]),
+    ("aomarl_pyr_set_modulation", _i, [_vp, _fp, _fp, _fp, _i, C.c_float]),
+    ("aomarl_pyr_set_ref", _i, [_vp, _fp]),
+    ("aomarl_pyr_measure", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     ("aomarl_groot_create", _i, [_vp, C.POINTER(C.c_void_p)]),
     ("aomarl_groot_destroy", _i, [_vp]),
     ("aomarl_groot_form", _i, [_vp, _vp, _vp, _vp, _i, _vp, _i, C.c_longlong, _vp]),
@@ -321,6 +326,16 @@ class PredictorDesc(C.Structure):
     """aomarl_predictor_desc (include/aomarl.h)"""
     _fields_ = [(n, C.c_int32) for n in ("nenv", "nmodes", "order", "nskip")] + \
                [("delay", C.c_float), ("forget", C.c_double), ("p0", C.c_double)]
+
+
+class PyrDesc(C.Structure):
+    """aomarl_pyr_desc (include/aomarl.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("nenv", "n", "Nfft", "nrebin", "nvalid", "npts_max", "pixel_filter", "batch_kib")] + \
+               [(n, C.c_float) for n in ("lambda_um", "nphotons", "noise", "thresh")] + \
+               [("mpupil", _fp), ("halfxy", _fp), ("submask", _fp), ("sincar", _fp), ("validsubsx", _ip), ("validsubsy", _ip)]
+
+
+PYR_NOISE = 1
 
 
 class PsfRecDesc(C.Structure):

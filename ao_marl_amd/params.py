@@ -79,7 +79,11 @@ class Param_wfs(_P):
     _defaults = dict(type=None, nxsub=0, npix=0, pixsize=0.0, Lambda=0.0, optthroughput=0.0,
                      fracsub=0.0, open_loop=False, atmos_seen=0, dms_seen=None, xpos=0.0, ypos=0.0,
                      gsalt=0.0, gsmag=0.0, zerop=0.0, noise=0.0, kernel=0.0, G=1.0, thetaML=0.0,
-                     dx=0.0, dy=0.0)
+                     dx=0.0, dy=0.0,
+                     # pyramid sensors (PWFS.py:194-222): modulation radius [lambda / D] and points, user-given
+                     # positions [arcsec], pupil separation, field stop [arcsec] and its shape
+                     pyr_ampl=0.0, pyr_npts=0, pyr_pos=None, pyr_pup_sep=-1, fssize=0.0, fstop=None, nPupils=0,
+                     pyr_misalignments=None)
 
     def __init__(self, roket=False, **kw):
         _P.__init__(self, **kw)
@@ -93,7 +97,9 @@ class Param_dm(_P):
 
 
 class Param_centroider(_P):
-    _defaults = dict(nwfs=None, type=None, thresh=1.0e-4, filter_TT=False)
+    # method: the pyramid centroider's (constants.py PyrCentroiderMethod: 0 no sinus / global, 1 sinus / global,
+    # 2 no sinus / local, 3 sinus / local normalisation)
+    _defaults = dict(nwfs=None, type=None, thresh=1.0e-4, filter_TT=False, method=1)
 
 
 class Param_controller(_P):

@@ -1054,6 +1054,50 @@ int aomarl_gemm_nt_batched(int batch, int M, int N, int K, const float *A, int l
                            long long strideBias, float *C, int ldc, long long strideC, int relu,
                            void *stream);
 
+/* Pyramid wavefront sensor ("pyrhr": four pupil images, modulation, field stop) looking at a pupil phase such as
+ * aomarl_raytrace_wfs leaves in st->wfs_phase.  The model is ao_marl_amd/pyramid.py:PyramidModel ("Pyramid
+ * sensor"); the geometry comes from geometry.pyr_geometry (reference: geom_init.py:init_pyrhr_geom).  Per environment
+ * and modulation point k:  f_k = mpupil exp(i (2 pi / lambda phi + cx_k (x - n/2) + cy_k (y - n/2))), centred in an
+ * Nfft^2 zero array;  F_k = fft2(f_k) exp(i halfxy) submask;  hr += w_k |ifft2 F_k|^2, k in index order.  Then the
+ * pixel filter (hr = Re ifft2(fft2(hr) sincar)), sums over nrebin x nrebin blocks, the flux scale
+ * nphotons / (sum_k w_k  sum mpupil^2), optional noise (the draw rule of the Shack-Hartmann pixels, one Philox block per
+ * (pixel, frame), idx = flat pixel index) and the slopes (all x, then all y).
+ * Arrays of the desc are HOST arrays, copied by create.  validsubsx / validsubsy: [4 nvalid], ROW and COLUMN of the
+ * pixel in the [Nfft / nrebin]^2 image, four blocks of nvalid in the reference's order (blocks at row-,col- / row+,col+
+ * / row+,col- / row-,col+ of the centre).  x slope of point i: ((q1 + q3) - (q0 + q2)) / norm, y slope:
+ * ((q1 + q2) - (q0 + q3)) / norm with q_j the pixel of block j. */
+typedef struct {
+  int32_t nenv, n, Nfft, nrebin, nvalid, npts_max, pixel_filter;
+  int32_t batch_kib;  /* KiB the intermediate planes of a batch may occupy; 0: the default (inside the last-level cache) */
+  float lambda_um;   /* wavelength of the sensor in microns (the phase is in microns) */
+  float nphotons;    /* photons per frame over the whole aperture */
+  float noise;       /* < 0: none; 0: photon noise; > 0: + read-out noise of that many electrons rms */
+  float thresh;      /* a normaliser below it gives slope 0 */
+  const float *mpupil;                     /* [n][n] */
+  const float *halfxy, *submask, *sincar;  /* [Nfft][Nfft], zero frequency at index 0 */
+  const int32_t *validsubsx, *validsubsy;  /* [4 nvalid] */
+} aomarl_pyr_desc;
+typedef struct aomarl_pyr aomarl_pyr;
+enum { AOMARL_PYR_NOISE = 1 };
+/* Allocates the whole workspace; nothing is allocated afterwards.  The modulation starts as one point on the tip
+ * (cx = cy = 0, weight 1, s_scale 1) and the reference slopes as zero. */
+int aomarl_pyr_create(const aomarl_pyr_desc *desc, aomarl_pyr **out);
+int aomarl_pyr_destroy(aomarl_pyr *p);
+/* cx, cy [rad / pixel of the pupil], w: HOST [npts], 1 <= npts <= npts_max; s_scale: the slopes' unit (arcsec).
+ * Synchronises the device. */
+int aomarl_pyr_set_modulation(aomarl_pyr *p, const float *cx, const float *cy, const float *w, int npts, float s_scale);
+/* ref: HOST [2 nvalid], subtracted from every slope vector; NULL: zero.  Synchronises the device. */
+int aomarl_pyr_set_ref(aomarl_pyr *p, const float *ref);
+/* phase: DEVICE [nenv][n * n] microns; environments env_begin .. env_begin + env_count - 1 are measured.
+ * image: DEVICE [nenv][(Nfft / nrebin)^2] or NULL; slopes: DEVICE [nenv][2 nvalid] or NULL (rows of the environments
+ * measured are written).  method 0 .. 3 (0 / 1: normalised by the mean intensity over the valid points, 2 / 3: by the
+ * point's own; 1 / 3: s_scale sin(pi / 2 raw), 0 / 2: s_scale raw).  flags & AOMARL_PYR_NOISE: the desc's noise is
+ * drawn with seeds[e] and frame[e] (DEVICE [nenv], as aomarl_state has them) and frame[e] advances by one.
+ * No atomics: every pixel is summed over the modulation points in index order by the thread that owns it, so the bits
+ * do not depend on how the environments are split into calls.  Asynchronous on `stream`; no allocation, no read-back. */
+int aomarl_pyr_measure(aomarl_pyr *p, const float *phase, int env_begin, int env_count, int flags, int method,
+                       const uint32_t *seeds, uint32_t *frame, float *image, float *slopes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
