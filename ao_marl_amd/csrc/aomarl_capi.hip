@@ -1035,3 +1035,4 @@ static DevState dev_state(const aomarl_state *st) {
 #include "aomarl_capi_step.hip"
 #include "aomarl_capi_extras.hip"
 #include "aomarl_capi_composites.hip"
+#include "aomarl_capi_dmreg.hip"

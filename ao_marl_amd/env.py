@@ -459,7 +459,9 @@ class VecRlSupervisor(object):
         if apply_control:
             # the stack-array shapes are left to the one-pass frame kernel when it can evaluate
             # them from the voltages (any other consumer materialises them on demand)
-            self.sim.apply_control(defer_shape=getattr(self.sim, "defer_shape", False) and not self.pure_delay_0)
+            # (... and never under a mis-registration: its trace reads the planes)
+            self.sim.apply_control(defer_shape=getattr(self.sim, "defer_shape", False) and not self.pure_delay_0 and
+                                   self.registration is None)
             if self.pure_delay_0:
                 self.sim.target_psf()           # raytrace_target behind apply_control (rlSupervisor.py:938-939)
         if snap and self.pure_delay_0:
@@ -482,7 +484,24 @@ class VecRlSupervisor(object):
         if defer_control and do_control:
             do_control = False
             self._control_pending = True
-        if self.pyramid is not None:
+        snapped = False
+        if self.registration is not None:
+            # a registration.DmRegistration is attached: the unfused frame with both traces through its table (move,
+            # target trace and PSF, sensor trace and image, the next move's prefetch, do_control)
+            reg = self.registration
+            self._move_or_keep(move_atmos)
+            reg.trace(target=True)
+            self.sim.target_psf_buffer()
+            reg.trace(target=False)
+            self.sim.comp_image(from_phase_buffer=True, noise=True, write_bincube=False, cog=True)
+            if self.keep_wfs_phase:             # the buffer holds the registered phase the sensor just saw
+                self._keep_wfs_phase_buffer()
+                snapped = True
+            if self.prefetch_atmos and move_atmos:
+                self.sim.prefetch_atmos()
+            if do_control:
+                self.sim.do_control()
+        elif self.pyramid is not None:
             # a pyramid.PyramidSensor is attached: the same frame with its measurement in place of the Shack-Hartmann's
             # (move, target PSF, the sensor's pupil phase, image and slopes, err = -cmat_pyr . slopes, com += gain err)
             self._move_or_keep(move_atmos)
@@ -524,7 +543,7 @@ class VecRlSupervisor(object):
                 self.sim.do_control()
         if self.geo is not None and do_control:
             self.geo.next_part_one_geo()            # next_part_one_geo, after controller 0 (:1038-1049)
-        if self.keep_wfs_phase:
+        if self.keep_wfs_phase and not snapped:
             self._snap_wfs_phase()
         self.iter += 1
 
@@ -541,6 +560,9 @@ class VecRlSupervisor(object):
             raise RuntimeError("keep_wfs_phase: the screens run one frame ahead (prefetch_atmos); build the "
                                "supervisor with prefetch_atmos=False")
         self.sim.raytrace_wfs(atm=True, dms=True, reset=True)
+        self._keep_wfs_phase_buffer()
+
+    def _keep_wfs_phase_buffer(self):
         ph = self.sim.t["wfs_phase"]
         if self._wfs_phase_frame is None or self._wfs_phase_frame.shape != ph.shape:
             self._wfs_phase_frame = torch.empty_like(ph)
@@ -577,6 +599,8 @@ class VecRlSupervisor(object):
 
     # a pyramid.PyramidSensor between its start() and stop(), or None
     pyramid = None
+    # a registration.DmRegistration between its start() and stop(), or None
+    registration = None
 
     def get_slopes(self):
         if self.pyramid is not None:
@@ -1123,6 +1147,7 @@ class VecAoEnv(object):
         return (self.native_step and self._native_glue and self._default_state_layout and
                 self.modal_shortcut and self._modal_valid and not linear_control and
                 sup.pyramid is None and                       # (a pyramid runs the call-by-call path)
+                sup.registration is None and                  # (so does a mirror mis-registration)
                 sup.geo is None and sup.gain is not None and not sup.pure_delay_0 and
                 not sup.keep_wfs_phase and not sup.keep_tar_image and not sup.keep_le_image and       # (the frame's sensor phase is snapped behind the Python next_part_one)
                 sup.freedom_vector is not None and not sup.next_part_one_split and

@@ -202,6 +202,11 @@ SYMBOLS = [
     ("aomarl_pyr_set_modulation", _i, [_vp, _fp, _fp, _fp, _i, C.c_float]),
     ("aomarl_pyr_set_ref", _i, [_vp, _fp]),
     ("aomarl_pyr_measure", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("aomarl_dmreg_create", _i, [_vp, _i, C.POINTER(C.c_void_p)]),
+    ("aomarl_dmreg_destroy", _i, [_vp]),
+    ("aomarl_dmreg_set", _i, [_vp, _i, _i, _i, _fp, _vp]),
+    ("aomarl_dmreg_get", _i, [_vp, _i, _i, _i, _fp, _vp]),
+    ("aomarl_dmreg_trace", _i, [_vp, _vp, C.POINTER(State), _i, _i, _i, _i, _vp]),
     ("aomarl_groot_create", _i, [_vp, C.POINTER(C.c_void_p)]),
     ("aomarl_groot_destroy", _i, [_vp]),
     ("aomarl_groot_form", _i, [_vp, _vp, _vp, _vp, _i, _vp, _i, C.c_longlong, _vp]),

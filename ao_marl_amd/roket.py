@@ -142,6 +142,9 @@ def _roket_supervisor(env):
     if sup.geo is None:
         raise RuntimeError("VecRoket: the fitting term and B come from the geometric twin; build the environment "
                            "with geo=True")
+    if getattr(sup, "registration", None) is not None:
+        raise RuntimeError("VecRoket: a mirror mis-registration is attached (DmRegistration.stop first): the breakdown's "
+                           "mirrors are the registered ones")
     if sup.pure_delay_0:
         raise NotImplementedError("VecRoket: modification_online (the pure-delay-0 call order) is not covered")
     if sup.autoencoder is not None:

@@ -673,6 +673,13 @@ class HipSim(object):
         self._ensure_shape()
         la.check(self.lib.aomarl_target_psf(self.ctx, C.byref(self.st), b, n, self._stream()))
 
+    def target_psf_buffer(self, env_begin=0, env_count=None):
+        """The short-exposure PSF window and Strehl of the phase a target trace left in the phase buffer
+        (aomarl_target_psf_buffer): aomarl_target_psf without its own trace."""
+        b, n = self._range(env_begin, env_count)
+        self._need_phase()
+        la.check(self.lib.aomarl_target_psf_buffer(self.ctx, C.byref(self.st), b, n, self._stream()))
+
     def target_image(self, env_begin=0, env_count=None):
         """Target.get_tar_image(expo_type="se") (targetCompass.py:71-92) of every environment of the range:
         [env_count, npsf, npsf], centred, raw |FFT2|^2 (aomarl_target_image: on demand, one environment at a time)."""

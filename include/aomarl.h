@@ -1098,6 +1098,37 @@ int aomarl_pyr_set_ref(aomarl_pyr *p, const float *ref);
 int aomarl_pyr_measure(aomarl_pyr *p, const float *phase, int env_begin, int env_count, int flags, int method,
                        const uint32_t *seeds, uint32_t *frame, float *image, float *slopes, void *stream);
 
+/* Mirror mis-registration per environment (reference: dmCompass.py:148-176, set_dm_registration(dm_index, dx, dy, theta,
+ * G), which forwards dx / pixsize, dy / pixsize, theta and G to the native mirror).  A table [nenv][ndm][6] of fp32
+ * numbers {A00, A01, A10, A11, tx, ty} on the device: pixel (x, y) of a source's grid (nn = n for the sensor, pupdiam for
+ * the target; c = (nn - 1) / 2; (ox, oy) the mirror's offset on that grid) samples mirror k of environment e at
+ *   (u, v) = (c + ox, c + oy) + A (x - c, y - c) + t
+ * by the bilinear rule of aomarl_raytrace_wfs / _target, unchanged (floor cell outside [0, dim): 0; neighbour index
+ * clamped at dim - 1; whole-pixel shortcut; tip-tilt planes evaluated from the two commands).  Four-parameter form:
+ * A = (1 / G) [[cos t, sin t], [-sin t, cos t]], t = -A (dx, dy) ("Mirror mis-registration").
+ * The object belongs to the context it was created with (reference: dmCompass.py:148-176). */
+typedef struct aomarl_dmreg aomarl_dmreg;
+/* Allocates the table for nenv environments of ctx's mirrors; it starts as the identity (dmCompass.py:148-176: the
+ * reference's defaults dx = dy = theta = 0, G = 1).  Refuses a context with a pipelined frame or a prefetched reset in
+ * flight.  Nothing is allocated afterwards. */
+int aomarl_dmreg_create(aomarl_ctx *ctx, int nenv, aomarl_dmreg **out);
+int aomarl_dmreg_destroy(aomarl_dmreg *r);
+/* Rows of mirror `dm` for environments env_begin .. env_begin + env_count - 1 (dmCompass.py:148-176).  At: HOST
+ * [env_count][6], copied before the call returns.  Refused by name: non-finite entries, |A_ij| > 4, |det A| outside
+ * [1/4, 4], |t| beyond 4 dim of the mirror, a bad range or mirror index -- so that no accepted table takes a coordinate
+ * near the int32 range; the kernel does not clamp.  The copy is ordered on `stream`, which is synchronised. */
+int aomarl_dmreg_set(aomarl_dmreg *r, int env_begin, int env_count, int dm, const float *At, void *stream);
+/* The same rows read back from the device into HOST At [env_count][6] (dmCompass.py:148-176 has no getter; the tests
+ * do).  Synchronises `stream`. */
+int aomarl_dmreg_get(aomarl_dmreg *r, int env_begin, int env_count, int dm, float *At, void *stream);
+/* aomarl_raytrace_wfs (target = 0, writes st->wfs_phase) or aomarl_raytrace_target (target = 1, st->tar_phase) with
+ * every mirror sampled through its row of the table (dmCompass.py:148-176); the atmosphere part and the
+ * AOMARL_TRACE_* flags mean what they mean there.  One kernel launch: layers and mirrors in one pass, one store per
+ * pixel.  Stack-array shapes a deferred apply_control left stale are materialised first.  Asynchronous on `stream`; no
+ * synchronisation, read-back or allocation. */
+int aomarl_dmreg_trace(aomarl_dmreg *r, aomarl_ctx *ctx, aomarl_state *st, int env_begin, int env_count, int target,
+                       int flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
