@@ -1036,3 +1036,4 @@ static DevState dev_state(const aomarl_state *st) {
 #include "aomarl_capi_extras.hip"
 #include "aomarl_capi_composites.hip"
 #include "aomarl_capi_dmreg.hip"
+#include "aomarl_lgs.hip"

@@ -629,6 +629,30 @@ __device__ __forceinline__ float bilinear_ring(const float *in, int N, int ox, i
   return (1.f - wy) * ((1.f - wx) * v00 + wx * v01) + wy * ((1.f - wx) * v10 + wx * v11);
 }
 
+// the mirrors of environment e seen from pixel (x, y) of the sensor's (TARGET: the target's) grid, added to v in
+// controller order: the mirror part of k_raytrace, shared with k_lgs_trace (aomarl_lgs.hip), whose layers alone differ
+template <bool TARGET>
+__device__ __forceinline__ float trace_dms(const DevSys &sys, const DevState &st, int e, int x, int y, float v) {
+  for (int k = 0; k < sys.ndm; k++) {
+    const DevDm &D = sys.dms[k];
+    const float fx = (float)x + (TARGET ? D.txo : D.wxo), fy = (float)y + (TARGET ? D.tyo : D.wyo);
+    const int ix = (int)floorf(fx), iy = (int)floorf(fy);
+    if (ix >= 0 && iy >= 0 && ix < D.dim && iy < D.dim) {
+      const float wx = fx - (float)ix, wy = fy - (float)iy;
+      const int ix1 = ix + 1 < D.dim ? ix + 1 : ix, iy1 = iy + 1 < D.dim ? iy + 1 : iy;
+      float v00 = dm_value(sys, st, e, k, ix, iy);
+      if (wx == 0.f && wy == 0.f) {
+        v += v00;
+      } else {
+        float v01 = dm_value(sys, st, e, k, ix1, iy), v10 = dm_value(sys, st, e, k, ix, iy1);
+        float v11 = dm_value(sys, st, e, k, ix1, iy1);
+        v += (1.f - wy) * ((1.f - wx) * v00 + wx * v01) + wy * ((1.f - wx) * v10 + wx * v11);
+      }
+    }
+  }
+  return v;
+}
+
 template <bool TARGET>
 __global__ __launch_bounds__(256) void k_raytrace(DevSys sys, DevState st, int env_begin,
                                                   int flags) {
@@ -649,23 +673,7 @@ __global__ __launch_bounds__(256) void k_raytrace(DevSys sys, DevState st, int e
     }
   }
   if (flags & AOMARL_TRACE_DMS) {
-    for (int k = 0; k < sys.ndm; k++) {
-      const DevDm &D = sys.dms[k];
-      const float fx = (float)x + (TARGET ? D.txo : D.wxo), fy = (float)y + (TARGET ? D.tyo : D.wyo);
-      const int ix = (int)floorf(fx), iy = (int)floorf(fy);
-      if (ix >= 0 && iy >= 0 && ix < D.dim && iy < D.dim) {
-        const float wx = fx - (float)ix, wy = fy - (float)iy;
-        const int ix1 = ix + 1 < D.dim ? ix + 1 : ix, iy1 = iy + 1 < D.dim ? iy + 1 : iy;
-        float v00 = dm_value(sys, st, e, k, ix, iy);
-        if (wx == 0.f && wy == 0.f) {
-          v += v00;
-        } else {
-          float v01 = dm_value(sys, st, e, k, ix1, iy), v10 = dm_value(sys, st, e, k, ix, iy1);
-          float v11 = dm_value(sys, st, e, k, ix1, iy1);
-          v += (1.f - wy) * ((1.f - wx) * v00 + wx * v01) + wy * ((1.f - wx) * v10 + wx * v11);
-        }
-      }
-    }
+    v = trace_dms<TARGET>(sys, st, e, x, y, v);
   }
   if (flags & AOMARL_TRACE_MASK) v *= (TARGET ? sys.spupil : sys.mpupil)[p];
   out[p] = v;

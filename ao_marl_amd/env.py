@@ -479,8 +479,8 @@ class VecRlSupervisor(object):
         self._err_stale = False
         if defer_control and getattr(self, "modal_predictor", None) is not None:
             defer_control = False               # the predictor is run by do_control: every frame has to reach it
-        if self.pyramid is not None:
-            defer_control = False               # err comes from the pyramid's own product: nothing to run on demand
+        if self.pyramid is not None or self.lgs is not None:
+            defer_control = False               # err comes from the sensor's own product: nothing to run on demand
         if defer_control and do_control:
             do_control = False
             self._control_pending = True
@@ -512,6 +512,21 @@ class VecRlSupervisor(object):
             self.pyramid.measure()
             if do_control:
                 self.pyramid.control()
+        elif self.lgs is not None:
+            # an lgs.LgsSensor is attached: the same frame seen through the cone by elongated spots (move, target PSF --
+            # the science target stays at infinity --, the cone trace, LGS image and slopes, err = -cmat_lgs . slopes,
+            # com += gain err)
+            self._move_or_keep(move_atmos)
+            self.sim.target_psf()
+            self.lgs.trace()
+            if self.prefetch_atmos and move_atmos:
+                self.sim.prefetch_atmos()
+            self.lgs.measure(write_cube=False)
+            if self.keep_wfs_phase:             # the buffer holds the phase the sensor just saw through the cone
+                self._keep_wfs_phase_buffer()
+                snapped = True
+            if do_control:
+                self.lgs.control()
         elif self.autoencoder is not None:
             # rlSupervisor.py:975-984 with the denoiser between image formation and centroiding;
             # the bincube never leaves the device (the reference copies it to the host and back)
@@ -601,10 +616,14 @@ class VecRlSupervisor(object):
     pyramid = None
     # a registration.DmRegistration between its start() and stop(), or None
     registration = None
+    # an lgs.LgsSensor between its start() and stop(), or None
+    lgs = None
 
     def get_slopes(self):
         if self.pyramid is not None:
             return self.pyramid.slopes
+        if self.lgs is not None:
+            return self.lgs.slopes
         return self.sim.slopes
 
     def get_err(self):
@@ -1123,7 +1142,7 @@ class VecAoEnv(object):
             sup.sim.volts2modes(sup.get_command(), out=self._ring[nxt])
         self._ring_pos = nxt
         if (self.residual_shortcut and self.modal_shortcut and sup.geo is None and sup.gain is not None
-                and sup.autoencoder is None and sup.pyramid is None and hasattr(sup.sim, "slopes2modes")):
+                and sup.autoencoder is None and sup.pyramid is None and sup.lgs is None and hasattr(sup.sim, "slopes2modes")):
             # the next control step rebuilds the command from Btt coordinates (rl_step below), so
             # the frame needs neither err nor the integrated command in actuator space: one product
             # with v2m . cmat instead of do_control + volts2modes; do_control runs on demand
@@ -1147,6 +1166,7 @@ class VecAoEnv(object):
         return (self.native_step and self._native_glue and self._default_state_layout and
                 self.modal_shortcut and self._modal_valid and not linear_control and
                 sup.pyramid is None and                       # (a pyramid runs the call-by-call path)
+                sup.lgs is None and                           # (so does a laser guide star)
                 sup.registration is None and                  # (so does a mirror mis-registration)
                 sup.geo is None and sup.gain is not None and not sup.pure_delay_0 and
                 not sup.keep_wfs_phase and not sup.keep_tar_image and not sup.keep_le_image and       # (the frame's sensor phase is snapped behind the Python next_part_one)
@@ -1353,7 +1373,8 @@ class VecAoEnv(object):
         it away (train_rpc.py:641); it is only evaluated here on request."""
         pair, out = None, None
         if (self.modal_shortcut and self._native_glue and self._default_state_layout and
-                self._modal_valid and not linear_control and self.supervisor.pyramid is None):
+                self._modal_valid and not linear_control and self.supervisor.pyramid is None and
+                self.supervisor.lgs is None):
             pair = (self._ring_slot(0), self._res_modes)
             out = self._ring_slot(-1)           # the slot the next linear_step makes the newest
         self.supervisor.next_part_two(action, linear_control=linear_control,

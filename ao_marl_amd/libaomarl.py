@@ -207,6 +207,12 @@ SYMBOLS = [
     ("aomarl_dmreg_set", _i, [_vp, _i, _i, _i, _fp, _vp]),
     ("aomarl_dmreg_get", _i, [_vp, _i, _i, _i, _fp, _vp]),
     ("aomarl_dmreg_trace", _i, [_vp, _vp, C.POINTER(State), _i, _i, _i, _i, _vp]),
+    ("aomarl_lgs_create", _i, [_vp, C.POINTER(C.c_void_p)]),
+    ("aomarl_lgs_destroy", _i, [_vp]),
+    ("aomarl_lgs_set_kernels", _i, [_vp, _fp]),
+    ("aomarl_lgs_set_ref", _i, [_vp, _fp]),
+    ("aomarl_lgs_trace", _i, [_vp, _vp, C.POINTER(State), _fp, _i, _i, _i, _i, _vp]),
+    ("aomarl_lgs_measure", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     ("aomarl_groot_create", _i, [_vp, C.POINTER(C.c_void_p)]),
     ("aomarl_groot_destroy", _i, [_vp]),
     ("aomarl_groot_form", _i, [_vp, _vp, _vp, _vp, _i, _vp, _i, C.c_longlong, _vp]),
@@ -341,6 +347,16 @@ class PyrDesc(C.Structure):
 
 
 PYR_NOISE = 1
+
+
+class LgsDesc(C.Structure):
+    """aomarl_lgs_desc (include/aomarl.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("nenv", "n", "pdiam", "N", "npix", "nrebin", "nvalid")] + \
+               [(n, C.c_float) for n in ("lambda_um", "nphotons", "noise", "cog_offset", "cog_scale")] + \
+               [("mpupil", _fp), ("halfxy", _fp), ("flux", _fp), ("sub_x0", _ip), ("sub_y0", _ip)]
+
+
+LGS_NOISE, LGS_WRITE_CUBE = 1, 2
 
 
 class PsfRecDesc(C.Structure):

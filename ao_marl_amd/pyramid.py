@@ -474,6 +474,8 @@ class PyramidSensor(object):
             raise RuntimeError(who + ": the supervisor has a pyramid attached already")
         if getattr(sup, "registration", None) is not None:
             raise RuntimeError(who + ": a mirror mis-registration is attached (DmRegistration.stop first)")
+        if getattr(sup, "lgs", None) is not None:
+            raise RuntimeError(who + ": a laser guide star is attached (LgsSensor.stop first)")
         sim = sup.sim
         if getattr(sim, "_twin", None) is not None:
             raise RuntimeError(who + ": the frame pipeline is on (the frames run a step ahead of the chains); build the "

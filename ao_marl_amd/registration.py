@@ -345,6 +345,8 @@ class DmRegistration(object):
             raise RuntimeError(who + ": the GEO twin (geo=True) traces registered mirrors of its own: not covered")
         if getattr(sup, "pyramid", None) is not None:
             raise RuntimeError(who + ": a pyramid is attached (PyramidSensor.stop first)")
+        if getattr(sup, "lgs", None) is not None:
+            raise RuntimeError(who + ": a laser guide star is attached (LgsSensor.stop first)")
         if getattr(sup, "autoencoder", None) is not None:
             raise RuntimeError(who + ": the denoiser (autoencoder) path is not covered")
         if getattr(sup, "keep_tar_image", False) or getattr(sup, "keep_le_image", False):

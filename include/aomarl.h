@@ -1129,6 +1129,59 @@ int aomarl_dmreg_get(aomarl_dmreg *r, int env_begin, int env_count, int dm, floa
 int aomarl_dmreg_trace(aomarl_dmreg *r, aomarl_ctx *ctx, aomarl_state *st, int env_begin, int env_count, int target,
                        int flags, void *stream);
 
+/* Laser guide star on the Shack-Hartmann sensor ("Laser guide star"; the model is ao_marl_amd/lgs.py:
+ * LgsModel and cone_trace_model).  The reference's host side is shesha/init/lgs_init.py; its native calls (lgs_init,
+ * lgs_update, lgs_makespot, the convolution in comp_image, the cone in raytrace) are not in the reference tree.
+ * Per (environment, sub-aperture k): the tile a = mask exp(i (2 pi / lambda phase - halfxy)), pdiam x pdiam, top-left
+ * phase pixel (sub_x0[k], sub_y0[k]);  I = |fft2(a zero-padded to N)|^2;  J = I circularly convolved with the kernel
+ * K_k [N][N];  sums of J over nrebin x nrebin blocks of the window of npix nrebin pixels centred on pixel N / 2 (the
+ * unrolled binmap, geom_init.py:751);  times nphotons flux[k] / (sum of the window);  optional noise (the draw rule of the
+ * Shack-Hartmann pixels, idx = flat index of the cube [nvalid][npix^2]);  centre of gravity
+ * (sum v x / sum v - cog_offset) cog_scale, all x then all y, minus the reference slopes.
+ * Arrays of the desc are HOST arrays, copied by create.  Sizes: pdiam = 16 with N = 64, and pdiam = 8 with N = 32; others
+ * are refused by name. */
+typedef struct {
+  int32_t nenv, n, pdiam, N, npix, nrebin, nvalid;
+  float lambda_um;   /* wavelength of the sensor in microns (the phase is in microns) */
+  float nphotons;    /* photons per frame and full sub-aperture */
+  float noise;       /* < 0: none; 0: photon noise; > 0: + read-out noise of that many electrons rms */
+  float cog_offset, cog_scale;
+  const float *mpupil;                     /* [n][n] */
+  const float *halfxy;                     /* [pdiam][pdiam] */
+  const float *flux;                       /* [nvalid] */
+  const int32_t *sub_x0, *sub_y0;          /* [nvalid] */
+} aomarl_lgs_desc;
+typedef struct aomarl_lgs aomarl_lgs;
+enum { AOMARL_LGS_NOISE = 1, AOMARL_LGS_WRITE_CUBE = 2 };
+/* Allocates everything (sensors.d_wfs[i].d_gs.d_lgs.lgs_init, lgs_init.py:309: the native object of the reference);
+ * nothing is allocated afterwards.  The kernels start as the impulse at (N / 2, N / 2) and the reference slopes as zero. */
+int aomarl_lgs_create(const aomarl_lgs_desc *desc, aomarl_lgs **out);
+int aomarl_lgs_destroy(aomarl_lgs *p);
+/* K: HOST [nvalid][N][N], finite, not negative, each with a positive sum (lgs_init.py:198, p_wfs._lgskern, which the
+ * reference uploads through lgs_init / lgs_update / lgs_makespot).  The device keeps, per sub-aperture, the table
+ * Kt(sy, sx) = sum_j K(j) exp(+2 pi i j . s / N), |sy| <= pdiam - 1, 0 <= sx <= pdiam - 1, formed here in double.
+ * Synchronises the device. */
+int aomarl_lgs_set_kernels(aomarl_lgs *p, const float *K);
+/* ref: HOST [2 nvalid], subtracted from every slope vector; NULL: zero (the reference's centroider's set_ref).
+ * Synchronises the device. */
+int aomarl_lgs_set_ref(aomarl_lgs *p, const float *ref);
+/* aomarl_raytrace_wfs through the cone (wfs_init.py:170-185, the gsalt terms of the offsets, and the native raytrace's
+ * cone): pixel (x, y) of the sensor's grid samples layer l at ((x, y) + (wxo, wyo)) + dm1[l] ((x, y) - (n - 1) / 2),
+ * dm1[l] = delta_l - 1 = -alt_l / gsalt (HOST [nlayers], in (-1, 0]), one fused multiply-add per coordinate, bilinear by
+ * the trace's rule; mirrors are traced as aomarl_raytrace_wfs traces them.  Writes st->wfs_phase of environments
+ * env_begin .. env_begin + env_count - 1; flags: AOMARL_TRACE_ATMOS | _DMS | _RESET.  dm1 = 0 gives aomarl_raytrace_wfs
+ * to the bit.  Asynchronous on `stream`; no synchronisation, read-back or allocation. */
+int aomarl_lgs_trace(aomarl_lgs *p, aomarl_ctx *ctx, aomarl_state *st, const float *dm1, int nlayers, int env_begin,
+                     int env_count, int flags, void *stream);
+/* The image and slopes (the reference's comp_image with its LGS convolution, then the centroider).  phase: DEVICE
+ * [nenv][n * n] microns; image: DEVICE [nenv][nvalid][npix^2], written with AOMARL_LGS_WRITE_CUBE; slopes: DEVICE
+ * [nenv][2 nvalid]; rows of the environments measured are written.  flags & AOMARL_LGS_NOISE: the desc's noise is drawn
+ * with seeds[e] and frame[e] (DEVICE [nenv], as aomarl_state has them) and frame[e] advances by one.  One workgroup per
+ * (environment, sub-aperture), no atomics, every sum in a fixed order: the bits do not depend on how the environments
+ * are split into calls.  Asynchronous on `stream`; no allocation, no read-back. */
+int aomarl_lgs_measure(aomarl_lgs *p, const float *phase, int env_begin, int env_count, int flags, const uint32_t *seeds,
+                       uint32_t *frame, float *image, float *slopes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
