@@ -328,10 +328,8 @@ class VecRlSupervisor(object):
             self.autoencoder.check_range()      # a saturated fp16 launch of the last episode is an error
         self.check_range()
         self.sim.reset(self.env_seeds())
-        if getattr(self, "online_modal_gains", None) is not None:
-            self.online_modal_gains.restart()   # the filters' history starts over; J and G carry across episodes
-        if getattr(self, "modal_predictor", None) is not None:
-            self.modal_predictor.restart()      # the predictors' history starts over; theta and P carry across episodes
+        if self.control_law is not None:
+            self.control_law.restart()          # its history starts over; what it has learned carries across episodes
         self._atmos_changed_behind = None
         self._rp_left = 0
         if self.reset_prefetch is not None:
@@ -459,9 +457,9 @@ class VecRlSupervisor(object):
         if apply_control:
             # the stack-array shapes are left to the one-pass frame kernel when it can evaluate
             # them from the voltages (any other consumer materialises them on demand)
-            # (... and never under a mis-registration: its trace reads the planes)
+            # (... and never under an attachment whose trace reads the planes)
             self.sim.apply_control(defer_shape=getattr(self.sim, "defer_shape", False) and not self.pure_delay_0 and
-                                   self.registration is None)
+                                   not (self.sensing is not None and self.sensing.row.reads_planes))
             if self.pure_delay_0:
                 self.sim.target_psf()           # raytrace_target behind apply_control (rlSupervisor.py:938-939)
         if snap and self.pure_delay_0:
@@ -477,56 +475,21 @@ class VecRlSupervisor(object):
         self._check_atmos_change()
         self.materialize_control()              # a frame still waiting for its do_control
         self._err_stale = False
-        if defer_control and getattr(self, "modal_predictor", None) is not None:
-            defer_control = False               # the predictor is run by do_control: every frame has to reach it
-        if self.pyramid is not None or self.lgs is not None:
-            defer_control = False               # err comes from the sensor's own product: nothing to run on demand
+        if (self.control_law is not None and self.control_law.row.every_frame) or self.own_control:
+            # every frame has to reach the control law inside do_control / err comes from the sensor's own product:
+            # nothing to run on demand
+            defer_control = False
         if defer_control and do_control:
             do_control = False
             self._control_pending = True
         snapped = False
-        if self.registration is not None:
-            # a registration.DmRegistration is attached: the unfused frame with both traces through its table (move,
-            # target trace and PSF, sensor trace and image, the next move's prefetch, do_control)
-            reg = self.registration
+        if self.sensing is not None:
+            # a sensing attachment: the move, its own frame (target trace and PSF, its trace and measurement of the
+            # sensor's phase, the next move's prefetch; True when it kept the frame's phase copy), its own control
             self._move_or_keep(move_atmos)
-            reg.trace(target=True)
-            self.sim.target_psf_buffer()
-            reg.trace(target=False)
-            self.sim.comp_image(from_phase_buffer=True, noise=True, write_bincube=False, cog=True)
-            if self.keep_wfs_phase:             # the buffer holds the registered phase the sensor just saw
-                self._keep_wfs_phase_buffer()
-                snapped = True
-            if self.prefetch_atmos and move_atmos:
-                self.sim.prefetch_atmos()
+            snapped = self.sensing.frame(move_atmos)
             if do_control:
-                self.sim.do_control()
-        elif self.pyramid is not None:
-            # a pyramid.PyramidSensor is attached: the same frame with its measurement in place of the Shack-Hartmann's
-            # (move, target PSF, the sensor's pupil phase, image and slopes, err = -cmat_pyr . slopes, com += gain err)
-            self._move_or_keep(move_atmos)
-            self.sim.target_psf()
-            self.sim.raytrace_wfs(atm=True, dms=True, reset=True)
-            if self.prefetch_atmos and move_atmos:
-                self.sim.prefetch_atmos()
-            self.pyramid.measure()
-            if do_control:
-                self.pyramid.control()
-        elif self.lgs is not None:
-            # an lgs.LgsSensor is attached: the same frame seen through the cone by elongated spots (move, target PSF --
-            # the science target stays at infinity --, the cone trace, LGS image and slopes, err = -cmat_lgs . slopes,
-            # com += gain err)
-            self._move_or_keep(move_atmos)
-            self.sim.target_psf()
-            self.lgs.trace()
-            if self.prefetch_atmos and move_atmos:
-                self.sim.prefetch_atmos()
-            self.lgs.measure(write_cube=False)
-            if self.keep_wfs_phase:             # the buffer holds the phase the sensor just saw through the cone
-                self._keep_wfs_phase_buffer()
-                snapped = True
-            if do_control:
-                self.lgs.control()
+                self.sensing.control()
         elif self.autoencoder is not None:
             # rlSupervisor.py:975-984 with the denoiser between image formation and centroiding;
             # the bincube never leaves the device (the reference copies it to the host and back)
@@ -612,19 +575,23 @@ class VecRlSupervisor(object):
     def _get_command0(self):
         return self.sim.com
 
-    # a pyramid.PyramidSensor between its start() and stop(), or None
-    pyramid = None
-    # a registration.DmRegistration between its start() and stop(), or None
-    registration = None
-    # an lgs.LgsSensor between its start() and stop(), or None
-    lgs = None
+    # The loop attachments, one slot per row of attachments.TABLE: the object between its start() and stop(), or None
+    # (pyramid.PyramidSensor, lgs.LgsSensor, registration.DmRegistration, modal_gains.OnlineModalGains,
+    # predictive.ModalPredictor) ...
+    pyramid = lgs = registration = online_modal_gains = modal_predictor = None
+    # ... and what attachments.attach / detach keep beside them: the attached object that senses and the one that is a
+    # control law (at most one of each: attachments.excludes), or None
+    sensing = control_law = None
+
+    @property
+    def own_control(self):
+        """An attached sensor forms err with its own command matrix (the flag of attachments.TABLE): no deferred
+        control, no residual shortcut and no modal pair (they stand on the supervisor's matrix; a mis-registration
+        keeps them, it runs the supervisor's do_control)."""
+        return self.sensing is not None and self.sensing.row.own_control
 
     def get_slopes(self):
-        if self.pyramid is not None:
-            return self.pyramid.slopes
-        if self.lgs is not None:
-            return self.lgs.slopes
-        return self.sim.slopes
+        return self.sensing.slopes if self.own_control else self.sim.slopes
 
     def get_err(self):
         self.materialize_control()
@@ -1142,7 +1109,7 @@ class VecAoEnv(object):
             sup.sim.volts2modes(sup.get_command(), out=self._ring[nxt])
         self._ring_pos = nxt
         if (self.residual_shortcut and self.modal_shortcut and sup.geo is None and sup.gain is not None
-                and sup.autoencoder is None and sup.pyramid is None and sup.lgs is None and hasattr(sup.sim, "slopes2modes")):
+                and sup.autoencoder is None and not sup.own_control and hasattr(sup.sim, "slopes2modes")):
             # the next control step rebuilds the command from Btt coordinates (rl_step below), so
             # the frame needs neither err nor the integrated command in actuator space: one product
             # with v2m . cmat instead of do_control + volts2modes; do_control runs on demand
@@ -1165,9 +1132,7 @@ class VecAoEnv(object):
         sup = self.supervisor
         return (self.native_step and self._native_glue and self._default_state_layout and
                 self.modal_shortcut and self._modal_valid and not linear_control and
-                sup.pyramid is None and                       # (a pyramid runs the call-by-call path)
-                sup.lgs is None and                           # (so does a laser guide star)
-                sup.registration is None and                  # (so does a mirror mis-registration)
+                sup.sensing is None and                       # (a sensing attachment runs the call-by-call path)
                 sup.geo is None and sup.gain is not None and not sup.pure_delay_0 and
                 not sup.keep_wfs_phase and not sup.keep_tar_image and not sup.keep_le_image and       # (the frame's sensor phase is snapped behind the Python next_part_one)
                 sup.freedom_vector is not None and not sup.next_part_one_split and
@@ -1373,8 +1338,7 @@ class VecAoEnv(object):
         it away (train_rpc.py:641); it is only evaluated here on request."""
         pair, out = None, None
         if (self.modal_shortcut and self._native_glue and self._default_state_layout and
-                self._modal_valid and not linear_control and self.supervisor.pyramid is None and
-                self.supervisor.lgs is None):
+                self._modal_valid and not linear_control and not self.supervisor.own_control):
             pair = (self._ring_slot(0), self._res_modes)
             out = self._ring_slot(-1)           # the slot the next linear_step makes the newest
         self.supervisor.next_part_two(action, linear_control=linear_control,

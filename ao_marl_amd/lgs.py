@@ -56,6 +56,8 @@ import numpy as np
 
 from . import libaomarl as la
 from . import params as P
+from .attachments import le_strehl
+from .loop_sensor import LoopSensor
 from .pyramid import pyr_noise
 
 __all__ = ["lgs_kernels", "lgs_profile", "lgs_nphotons", "cone_deltas", "cone_trace_model", "LgsModel", "NativeLgs",
@@ -472,7 +474,7 @@ class _ModelBackend(object):
 
 
 # ------------------------------------------------------------------------------------------------ the sensor
-class LgsSensor(object):
+class LgsSensor(LoopSensor):
     """A laser guide star on the guide star of a VecRlSupervisor's NGS Shack-Hartmann system.
 
         lgs = LgsSensor(sup, gsalt=90e3, llt=(0., 0.))
@@ -483,6 +485,7 @@ class LgsSensor(object):
 
     Values default to attributes of p_wfss[0] where it has them.  kernels: K [nvalid][N][N] in place of the elongation
     kernel (lgs.impulse_kernels: the NGS spots through the cone)."""
+    slot = "lgs"
 
     def __init__(self, sup, gsalt=None, llt=None, beamsize=None, profile=None, laserpower=None, lgsreturnperwatt=None,
                  noise=None, kernels=None):
@@ -526,14 +529,6 @@ class LgsSensor(object):
         self.cmat, self.ref, self.linearity, self._cmat_dev, self._attached = None, None, None, None, False
 
     # ---- measurements
-    @property
-    def image(self):
-        return self.native.image
-
-    @property
-    def slopes(self):
-        return self.native.slopes
-
     def trace(self, atm=True, dms=True, env_begin=0, env_count=None):
         """The sensor's pupil phase of the simulator's state through the cone, into the simulator's phase buffer."""
         self.native.trace(self.sup.sim, self.deltas, atm, dms, env_begin, env_count)
@@ -550,10 +545,6 @@ class LgsSensor(object):
         return self.native.measure(phase, noisy, sim.t["seeds"] if noisy else None, sim.t["frame"] if noisy else None,
                                    env_begin, env_count, write_cube)
 
-    def set_ref(self, ref=None):
-        self.native.set_ref(ref)
-        self.ref = None if ref is None else np.asarray(ref, dtype=np.float32).copy()
-
     def set_kernels(self, kernels):
         if self._attached:
             raise RuntimeError("set_kernels: stop() first")
@@ -561,143 +552,42 @@ class LgsSensor(object):
         self.kernels = np.asarray(kernels, dtype=np.float64)
         self.cmat, self._cmat_dev = None, None
 
-    # ---- calibration
-    def _volts(self, volts):
-        import torch
-        sim = self.sup.sim
-        v = np.zeros((sim.nenv, volts.shape[1]), dtype=np.float32)
-        v[:volts.shape[0]] = volts
-        return v if self.device == "cpu" else torch.from_numpy(v).to(sim.device)
+    # ---- what LoopSensor asks for (in the calibration the mirrors are in the pupil: the cone does not touch them)
+    keeps_phase = True                          # the buffer holds the phase the sensor just saw through the cone
 
-    def _host(self, t, nn):
-        return np.asarray(t[:nn], dtype=np.float64) if self.device == "cpu" else t[:nn].double().cpu().numpy()
+    def _pupil(self):
+        return np.asarray(self.s.mpupil).reshape(-1) != 0
 
-    def _response(self, volts, rms=False):
-        """Noise-free slopes [K][nslope] (float64, host) of the commands volts [K][nactu], atmosphere off (the mirrors
-        are in the pupil: the cone does not touch them); rms: the rms of the pupil phase instead."""
-        sim, K = self.sup.sim, volts.shape[0]
-        out = np.zeros(K) if rms else np.zeros((K, self.nslope))
-        pup = np.asarray(self.s.mpupil).reshape(-1) != 0
-        for k0 in range(0, K, sim.nenv):
-            nn = min(sim.nenv, K - k0)
-            sim.comp_dm_shape(self._volts(volts[k0:k0 + nn]))
-            sim.raytrace_wfs(atm=False, dms=True, reset=True)
-            if rms:
-                ph = self._host(sim.t["wfs_phase"].reshape(sim.nenv, -1), nn)[:, pup]
-                out[k0:k0 + nn] = np.sqrt(((ph - ph.mean(axis=1, keepdims=True))**2).mean(axis=1))
-            else:
-                self.measure(noise=False, write_cube=False)
-                out[k0:k0 + nn] = self._host(self.native.slopes, nn)
-        return out
+    def _quiet(self):
+        self.measure(noise=False, write_cube=False)
+
+    def _trace(self):
+        self.trace()
+
+    def _measure(self):
+        self.measure(write_cube=False)
 
     def calibrate(self, push_um=0.01):
-        """Flat reference slopes, the Btt modes pushed and pulled through the mirrors by `push_um` microns rms of phase
-        each, the same with twice the push -- `self.linearity` is the largest relative deviation of a mode's response
-        per unit push between the two -- and the command matrix through modal.cmat_with_btt with the supervisor's
-        filtered-mode count.  Leaves the mirrors of the simulator as its voltages say.  Returns cmat_lgs
-        [nactu][nslope]."""
-        from . import modal
-        sup = self.sup
-        if self._attached:
-            raise RuntimeError("calibrate: stop() first")
         if not push_um > 0:
             raise ValueError("calibrate: push_um = %r must be positive" % (push_um,))
-        m2v = np.asarray(sup.modes2volts, dtype=np.float64)             # [nactu][nmodes]
-        v2m = np.asarray(sup.volts2modes, dtype=np.float64)             # [nmodes][nactu]
-        self.native.set_ref(None)
-        flat = self._response(np.zeros((1, m2v.shape[0])))[0]
-        self.set_ref(flat)
-        a = push_um / np.maximum(self._response(m2v.T, rms=True), 1e-30)
-        cmds = m2v.T * a[:, None]
-        d1 = (self._response(cmds) - self._response(-cmds)) / (2 * a[:, None])
-        d2 = (self._response(2 * cmds) - self._response(-2 * cmds)) / (4 * a[:, None])
-        n1 = np.linalg.norm(d1, axis=1)
-        self.linearity = float(np.max(np.linalg.norm(d2 - d1, axis=1) / np.maximum(n1, 1e-300)))
-        self.push = a
-        self.imat_modes = d1.T                                          # [nslope][nmodes]
-        nfilt = max(int(getattr(sup, "n_reverse_filtered_from_cmat", 0)), 0)
-        self.cmat = modal.cmat_with_btt(self.imat_modes @ v2m, m2v, nfilt)
-        self._cmat_dev = None
-        if self.device == "cpu":                                       # the mirrors back on the loop's voltages
-            sup.sim.comp_dm_shape(np.asarray(sup.sim.voltage)[:, :self.s.nactu])
-        else:
-            sup.sim.comp_dm_shape()
-        return self.cmat
+        return LoopSensor.calibrate(self, push_um)
 
     # ---- the loop
     def start(self):
-        """Attach: the supervisor's next_part_one measures with this sensor (see VecRlSupervisor.next_part_one)."""
-        sup, who = self.sup, "LgsSensor.start"
-        if self.cmat is None:
-            raise RuntimeError(who + ": calibrate() first")
-        if getattr(sup, "lgs", None) is not None:
-            raise RuntimeError(who + ": the supervisor has an LGS attached already")
-        if getattr(sup, "pyramid", None) is not None:
-            raise RuntimeError(who + ": a pyramid is attached (PyramidSensor.stop first)")
-        if getattr(sup, "registration", None) is not None:
-            raise RuntimeError(who + ": a mirror mis-registration is attached (DmRegistration.stop first)")
-        sim = sup.sim
-        if getattr(sim, "_twin", None) is not None:
-            raise RuntimeError(who + ": the frame pipeline is on (the frames run a step ahead of the chains); build the "
-                               "environment with frame_pipeline=False")
-        if sup.reset_prefetch is not None:
-            raise RuntimeError(who + ": a prefetched reset is set (reset_prefetch): not covered")
-        if sup.pure_delay_0:
-            raise NotImplementedError(who + ": modification_online (the pure-delay-0 call order) is not covered")
-        if sup.autoencoder is not None:
-            raise RuntimeError(who + ": the denoiser is trained on NGS spots and reads the simulator's cube, not the "
-                               "LGS sensor's")
-        if sup.geo is not None:
-            raise RuntimeError(who + ": the GEO twin (geo=True) is not covered")
-        if sup.modal_gains is not None:
-            raise RuntimeError(who + ": modal gains are set (set_modal_gains(None) first): the LGS loop is the scalar "
-                               "integrator")
-        if getattr(sup, "online_modal_gains", None) is not None:
-            raise RuntimeError(who + ": an on-line modal-gain optimiser is attached (OnlineModalGains.stop first)")
-        if getattr(sup, "modal_predictor", None) is not None:
-            raise RuntimeError(who + ": a modal predictor is attached (ModalPredictor.stop first)")
-        if sup.gain is None:
-            raise RuntimeError(who + ": the supervisor has per-environment gains (set_gain with a vector); set one "
-                               "scalar gain first")
-        if self.device == "cpu" and getattr(sim, "sims", None) is None:
-            raise NotImplementedError(who + ": the loop on the CPU needs a simulator with one oracle per environment")
-        if self.device != "cpu" and self._cmat_dev is None:
-            import torch
-            self._cmat_dev = torch.as_tensor(np.ascontiguousarray(self.cmat, dtype=np.float32), device=sim.device)
-        sup.materialize_control()
-        sup.lgs, self._attached = self, True
-        return self
-
-    def stop(self):
-        if not self._attached:
-            return
-        if getattr(self.sup, "lgs", None) is self:
-            self.sup.lgs = None
-        self._attached = False
+        if self.device == "cpu" and getattr(self.sup.sim, "sims", None) is None:
+            raise NotImplementedError("LgsSensor.start: the loop on the CPU needs a simulator with one oracle per environment")
+        return LoopSensor.start(self)
 
     def control(self):
-        """err = -cmat_lgs . slopes into the state's err, com += gain err (the supervisor's branch calls it)."""
-        sup, sim = self.sup, self.sup.sim
-        if self.device == "cpu":                # one oracle per environment: its err and com, as aoref_ls_control leaves them
-            cm = np.ascontiguousarray(self.cmat, dtype=np.float32)
-            for o, sl in zip(sim.sims, np.ascontiguousarray(self.native.slopes, dtype=np.float32)):
-                o.L.aoref_ls_control(cm, cm.shape[0], cm.shape[1], sl, float(sup.gain), o.err, o.com)
-            return
-        sim.gemm_nt(self.native.slopes, self._cmat_dev, alpha=-1.0, beta=0.0, Cout=sim.err)
-        sim.com.add_(sim.err, alpha=float(sup.gain))
+        if self.device != "cpu":
+            return LoopSensor.control(self)
+        # one oracle per environment: its err and com, as aoref_ls_control leaves them
+        cm = np.ascontiguousarray(self.cmat, dtype=np.float32)
+        for o, sl in zip(self.sup.sim.sims, np.ascontiguousarray(self.native.slopes, dtype=np.float32)):
+            o.L.aoref_ls_control(cm, cm.shape[0], cm.shape[1], sl, float(self.sup.gain), o.err, o.com)
 
 
 # ------------------------------------------------------------------------------------------------ command line
-def _le_strehl(sup, nframes):
-    """long-exposure Strehl (mean over the environments) of `nframes` integrator frames behind a reset"""
-    sup.reset()
-    sup.next_part_one()
-    for _ in range(nframes):
-        sup.next_part_two(None, linear_control=True)
-        sup.next_part_one()
-    return float(sup.get_strehl()[:, 1].mean())
-
-
 def main(argv=None):
     import argparse
     from .env import VecRlSupervisor
@@ -720,12 +610,12 @@ def main(argv=None):
     side = tuple(a.llt) if a.llt is not None else (float(ps.p_tel.diam), 0.)
     print("config %s, %d environments, %d frames, gain %g, %d modes filtered, gsalt %g m" % (
         ps.simul_name, a.envs, a.frames, sup.gain, a.nfilt, a.gsalt))
-    print("long-exposure Strehl  NGS SH integrator %.4f" % _le_strehl(sup, a.frames))
+    print("long-exposure Strehl  NGS SH integrator %.4f" % le_strehl(sup, a.frames))
     for name, llt in (("centre launch", (0., 0.)), ("side launch (%g, %g) m" % side, side)):
         lgs = LgsSensor(sup, gsalt=a.gsalt, llt=llt, beamsize=a.beamsize)
         lgs.calibrate()
         lgs.start()
-        sr = _le_strehl(sup, a.frames)
+        sr = le_strehl(sup, a.frames)
         lgs.stop()
         print("long-exposure Strehl  LGS loop, %-28s %.4f   (doubled-push deviation %.3g)" % (name, sr, lgs.linearity))
     return 0

@@ -32,6 +32,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import attachments
 from . import libaomarl as la
 
 __all__ = ["gain_grid", "delay_weights", "stable", "pole_radius", "argmin_gain", "LoopBank", "loop_rejection",
@@ -388,17 +389,7 @@ class NativeOnlineLoopBank(object):
 
 def _open_loop_supervisor(sup, who="record_open_loop"):
     """Refuses the supervisor states in which a frame's slopes are not the ones the call order just measured."""
-    sim = sup.sim
-    if getattr(sup, "reset_prefetch", None) is not None:
-        raise RuntimeError("%s: a prefetched reset (reset_prefetch=%r) is not supported while recording"
-                           % (who, sup.reset_prefetch,))
-    if getattr(sim, "_twin", None) is not None:
-        raise RuntimeError("%s: the frame pipeline is enabled on this simulator: slopes of odd frames "
-                           "live in its twin; switch it off behind a reset (enable_frame_pipeline(False))" % who)
-    if sup.pure_delay_0:
-        raise NotImplementedError("%s: modification_online (the pure-delay-0 call order) is not covered" % who)
-    if sup.autoencoder is not None:
-        raise NotImplementedError("%s: autoencoder: the loop model has no denoiser" % who)
+    attachments.refuse(sup, who, attachments.OPEN_LOOP)
     return sup
 
 
@@ -411,6 +402,8 @@ class OnlineModalGains(object):
         opt = OnlineModalGains(sup, period=256, horizon=2048).start()
         ... run the loop; sup.reset() restarts the filters, J and G carry over ...
         opt.G, opt.updates;  opt.stop()"""
+    slot = "online_modal_gains"
+    row = attachments.TABLE[slot]
 
     def __init__(self, sup, gains=None, nskip=50, period=256, horizon=None, beta=1.0, pool="all", native=True, chunk=32):
         self.sup = sup
@@ -429,16 +422,8 @@ class OnlineModalGains(object):
         sup = self.sup
         if self.bank is not None:
             raise RuntimeError("OnlineModalGains.start: already started")
-        if getattr(sup, "online_modal_gains", None) is not None:
-            raise RuntimeError("OnlineModalGains.start: the supervisor has an on-line optimiser attached already")
-        if getattr(sup, "modal_predictor", None) is not None:
-            raise RuntimeError("OnlineModalGains.start: a modal predictor is attached (predictive.ModalPredictor.stop "
-                               "first): it replaces the integrator whose gains this optimises")
-        _open_loop_supervisor(sup, "OnlineModalGains.start")
+        attachments.check(sup, self.slot)
         g = sup.gain
-        if g is None:
-            raise RuntimeError("OnlineModalGains.start: the supervisor has per-environment gains (set_gain with a vector); "
-                               "set one scalar gain first")
         if not float(g) > 0.0:
             raise RuntimeError("OnlineModalGains.start: the supervisor's gain is %r: no factor on it gives G" % (g,))
         mgain = sup.modal_gains
@@ -457,7 +442,7 @@ class OnlineModalGains(object):
             self.bank.attach(sup.sim)
         else:
             self.bank = OnlineLoopBank(self.gains, self.delay, self.nskip, self.period, self.forget, self.beta, self.pool, G0)
-        sup.online_modal_gains = self
+        attachments.attach(sup, self.slot, self)        # (checked above: the bank exists before the slot holds it)
         return self
 
     def observe(self):
@@ -479,8 +464,7 @@ class OnlineModalGains(object):
             return
         if self.native:
             self.bank.detach()
-        if getattr(self.sup, "online_modal_gains", None) is self:
-            self.sup.online_modal_gains = None
+        attachments.detach(self.sup, self.slot, self)
         self._final = (self.G, self.J, self.updates)
         self.bank = None
 

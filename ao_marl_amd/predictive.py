@@ -34,8 +34,9 @@ import ctypes as C
 
 import numpy as np
 
+from . import attachments
 from . import libaomarl as la
-from .modal_gains import _open_loop_supervisor, delay_weights, record_open_loop
+from .modal_gains import delay_weights, record_open_loop
 
 __all__ = ["MAX_ORDER", "PredictorBank", "NativePredictorBank", "ModalPredictor", "warm_start"]
 
@@ -285,6 +286,8 @@ class ModalPredictor(object):
         pred.warm_start(2048); pred.freeze()      # optional: a trained, frozen filter
         ... run the loop; sup.reset() restarts the history, theta and P carry over ...
         pred.theta, pred.rejection;  pred.stop()"""
+    slot = "modal_predictor"
+    row = attachments.TABLE[slot]
 
     def __init__(self, sup, order=4, horizon=None, p0=1e4, nskip=50, native=True):
         self.sup = sup
@@ -307,15 +310,7 @@ class ModalPredictor(object):
         sup = self.sup
         if self.bank is not None:
             raise RuntimeError("ModalPredictor.start: already started")
-        if getattr(sup, "modal_predictor", None) is not None:
-            raise RuntimeError("ModalPredictor.start: the supervisor has a predictor attached already")
-        if getattr(sup, "online_modal_gains", None) is not None:
-            raise RuntimeError("ModalPredictor.start: an on-line modal-gain optimiser is attached (OnlineModalGains.stop "
-                               "first): the predictor replaces the integrator whose gains it optimises")
-        _open_loop_supervisor(sup, "ModalPredictor.start")
-        if sup.gain is None:
-            raise RuntimeError("ModalPredictor.start: the supervisor has per-environment gains (set_gain with a vector); "
-                               "set one scalar gain first")
+        attachments.check(sup, self.slot)
         if float(sup.gain) == 0.0:
             raise RuntimeError("ModalPredictor.start: the supervisor's gain is 0: a do_control with gain 0 computes err "
                                "alone and is not a frame of the loop")
@@ -329,7 +324,7 @@ class ModalPredictor(object):
         else:
             bank.push(np.zeros((0, sup.sim.nenv, sup.nmodes)))       # (shapes the statement)
         self.bank = bank
-        sup.modal_predictor = self
+        attachments.attach(sup, self.slot, self)        # (checked above: the bank exists before the slot holds it)
         return self
 
     def observe(self):
@@ -385,8 +380,7 @@ class ModalPredictor(object):
         self._final = (self.theta, self.P, self.J, self.J0)
         if self.native:
             self.bank.detach()
-        if getattr(self.sup, "modal_predictor", None) is self:
-            self.sup.modal_predictor = None
+        attachments.detach(self.sup, self.slot, self)
         if self._set_gains:
             self.sup.set_modal_gains(None)
             self._set_gains = False

@@ -38,6 +38,8 @@ import numpy as np
 from . import geometry as G
 from . import libaomarl as la
 from . import params as P
+from .attachments import le_strehl
+from .loop_sensor import LoopSensor
 
 __all__ = ["PyramidModel", "NativePyramid", "PyramidSensor", "pyr_noise"]
 
@@ -287,7 +289,7 @@ def _pyr_params(nxsub, pyr_ampl, pyr_npts, fssize, fstop, Lambda, gsmag, noise, 
                        fracsub=like.fracsub, atmos_seen=1, xpos=like.xpos, ypos=like.ypos)
 
 
-class PyramidSensor(object):
+class PyramidSensor(LoopSensor):
     """A pyramid on the guide star of a VecRlSupervisor's system.
 
         pyr = PyramidSensor(sup, nxsub=20)
@@ -297,6 +299,7 @@ class PyramidSensor(object):
         pyr.stop()
 
     PyramidSensor.from_geometry(...) builds one without a supervisor (measure(phase) only)."""
+    slot = "pyramid"
 
     def __init__(self, sup, nxsub=None, pyr_ampl=3, pyr_npts=16, fssize=None, fstop="round", Lambda=None, gsmag=None,
                  noise=-1, method=1, thresh=1.0e-4, pixel_filter=True):
@@ -368,14 +371,6 @@ class PyramidSensor(object):
         return scale
 
     # ---- measurements
-    @property
-    def image(self):
-        return self.native.image
-
-    @property
-    def slopes(self):
-        return self.native.slopes
-
     def measure(self, phase=None, noise=None, env_begin=0, env_count=None):
         """Slopes [nenv][2 nvalid] (device) of `phase` (default: the simulator's sensor phase, as raytrace_wfs left
         it).  noise (default: whenever the sensor has noise and a simulator whose counters it can use)."""
@@ -390,147 +385,22 @@ class PyramidSensor(object):
         return self.native.measure(phase, self.method, noisy, sim.t["seeds"] if noisy else None,
                                    sim.t["frame"] if noisy else None, env_begin, env_count)
 
-    def set_ref(self, ref=None):
-        self.native.set_ref(ref)
-        self.ref = None if ref is None else np.asarray(ref, dtype=np.float32).copy()
+    # ---- what LoopSensor asks for (the calibration pushes `push_um` small against the modulation radius: pyr_ampl
+    # lambda / D of tilt is pyr_ampl lambda / 4 rms)
+    def _pupil(self):
+        return np.asarray(self.pg.mpupil).reshape(-1) != 0
 
-    # ---- calibration
-    def _response(self, volts):
-        """Noise-free slopes [K][nslope] (float64, host) of the commands volts [K][nactu], atmosphere off."""
-        import torch
-        sim, K = self.sup.sim, volts.shape[0]
-        out = np.zeros((K, self.nslope))
-        for k0 in range(0, K, sim.nenv):
-            nn = min(sim.nenv, K - k0)
-            v = torch.zeros(sim.nenv, volts.shape[1], dtype=torch.float32, device=sim.device)
-            v[:nn] = torch.from_numpy(np.ascontiguousarray(volts[k0:k0 + nn], dtype=np.float32)).to(sim.device)
-            sim.comp_dm_shape(v)
-            sim.raytrace_wfs(atm=False, dms=True, reset=True)
-            self.measure(noise=False)
-            out[k0:k0 + nn] = self.native.slopes[:nn].double().cpu().numpy()
-        return out
+    def _quiet(self):
+        self.measure(noise=False)
 
-    def calibrate(self, push_um=0.01):
-        """Flat reference slopes, the Btt modes pushed and pulled through the mirrors by `push_um` microns rms of
-        phase each (small against the modulation radius: pyr_ampl lambda / D of tilt is pyr_ampl lambda / 4 rms), the
-        same with twice the push -- `self.linearity` is the largest relative deviation of a mode's response per unit
-        push between the two -- and the command matrix through modal.cmat_with_btt with the supervisor's filtered-mode
-        count.  Leaves the mirrors of the simulator as the supervisor's voltages say.  Returns cmat_pyr
-        [nactu][nslope]."""
-        from . import modal
-        sup = self.sup
-        if sup is None:
-            raise RuntimeError("calibrate: a stand-alone sensor has no mirrors")
-        if self._attached:
-            raise RuntimeError("calibrate: stop() first")
-        m2v = np.asarray(sup.modes2volts, dtype=np.float64)             # [nactu][nmodes]
-        v2m = np.asarray(sup.volts2modes, dtype=np.float64)             # [nmodes][nactu]
-        nm = m2v.shape[1]
-        self.native.set_ref(None)
-        flat = self._response(np.zeros((1, m2v.shape[0])))[0]
-        self.set_ref(flat)
-        # rms of the sensor's pupil phase per unit of each mode: the Btt modes are orthonormal for the geometric
-        # covariance (modal.compute_btt), measured here rather than assumed
-        rms = self._phase_rms(m2v.T)
-        a = push_um / np.maximum(rms, 1e-30)
-        cmds = m2v.T * a[:, None]
-        d1 = (self._response(cmds) - self._response(-cmds)) / (2 * a[:, None])
-        d2 = (self._response(2 * cmds) - self._response(-2 * cmds)) / (4 * a[:, None])
-        n1 = np.linalg.norm(d1, axis=1)
-        self.linearity = float(np.max(np.linalg.norm(d2 - d1, axis=1) / np.maximum(n1, 1e-300)))
-        self.push = a
-        Dm = d1.T                                                       # [nslope][nmodes]
-        self.imat_modes = Dm
-        nfilt = max(int(getattr(sup, "n_reverse_filtered_from_cmat", 0)), 0)
-        self.cmat = modal.cmat_with_btt(Dm @ v2m, m2v, nfilt)
-        self._cmat_dev = None
-        sup.sim.comp_dm_shape()                                         # the mirrors back on the loop's voltages
-        return self.cmat
+    def _trace(self):
+        self.sup.sim.raytrace_wfs(atm=True, dms=True, reset=True)
 
-    def _phase_rms(self, volts):
-        import torch
-        sim, K = self.sup.sim, volts.shape[0]
-        pup = torch.as_tensor(np.asarray(self.pg.mpupil).reshape(-1) != 0, device=sim.device)
-        out = np.zeros(K)
-        for k0 in range(0, K, sim.nenv):
-            nn = min(sim.nenv, K - k0)
-            v = torch.zeros(sim.nenv, volts.shape[1], dtype=torch.float32, device=sim.device)
-            v[:nn] = torch.from_numpy(np.ascontiguousarray(volts[k0:k0 + nn], dtype=np.float32)).to(sim.device)
-            sim.comp_dm_shape(v)
-            sim.raytrace_wfs(atm=False, dms=True, reset=True)
-            ph = sim.t["wfs_phase"].reshape(sim.nenv, -1)[:nn][:, pup].double()
-            out[k0:k0 + nn] = (ph - ph.mean(dim=1, keepdim=True)).pow(2).mean(dim=1).sqrt().cpu().numpy()
-        return out
-
-    # ---- the loop
-    def start(self):
-        """Attach: the supervisor's next_part_one measures with this sensor (see VecRlSupervisor.next_part_one)."""
-        sup, who = self.sup, "PyramidSensor.start"
-        if sup is None:
-            raise RuntimeError(who + ": a stand-alone sensor has no loop")
-        if self.cmat is None:
-            raise RuntimeError(who + ": calibrate() first")
-        if getattr(sup, "pyramid", None) is not None:
-            raise RuntimeError(who + ": the supervisor has a pyramid attached already")
-        if getattr(sup, "registration", None) is not None:
-            raise RuntimeError(who + ": a mirror mis-registration is attached (DmRegistration.stop first)")
-        if getattr(sup, "lgs", None) is not None:
-            raise RuntimeError(who + ": a laser guide star is attached (LgsSensor.stop first)")
-        sim = sup.sim
-        if getattr(sim, "_twin", None) is not None:
-            raise RuntimeError(who + ": the frame pipeline is on (the frames run a step ahead of the chains); build the "
-                               "environment with frame_pipeline=False")
-        if sup.reset_prefetch is not None:
-            raise RuntimeError(who + ": a prefetched reset is set (reset_prefetch): not covered")
-        if sup.pure_delay_0:
-            raise NotImplementedError(who + ": modification_online (the pure-delay-0 call order) is not covered")
-        if sup.autoencoder is not None:
-            raise RuntimeError(who + ": the denoiser works on Shack-Hartmann spots, not on a pyramid")
-        if sup.geo is not None:
-            raise RuntimeError(who + ": the GEO twin (geo=True) is not covered")
-        if sup.modal_gains is not None:
-            raise RuntimeError(who + ": modal gains are set (set_modal_gains(None) first): the pyramid's loop is the "
-                               "scalar integrator")
-        if getattr(sup, "online_modal_gains", None) is not None:
-            raise RuntimeError(who + ": an on-line modal-gain optimiser is attached (OnlineModalGains.stop first)")
-        if getattr(sup, "modal_predictor", None) is not None:
-            raise RuntimeError(who + ": a modal predictor is attached (ModalPredictor.stop first)")
-        if sup.gain is None:
-            raise RuntimeError(who + ": the supervisor has per-environment gains (set_gain with a vector); set one "
-                               "scalar gain first")
-        import torch
-        if self._cmat_dev is None:
-            self._cmat_dev = torch.as_tensor(np.ascontiguousarray(self.cmat, dtype=np.float32), device=sim.device)
-        sup.materialize_control()
-        sup.pyramid, self._attached = self, True
-        return self
-
-    def stop(self):
-        if not self._attached:
-            return
-        sup = self.sup
-        if getattr(sup, "pyramid", None) is self:
-            sup.pyramid = None
-        self._attached = False
-
-    def control(self):
-        """err = -cmat_pyr . slopes into the state's err, com += gain err (the supervisor's branch calls it)."""
-        sup, sim = self.sup, self.sup.sim
-        sim.gemm_nt(self.native.slopes, self._cmat_dev, alpha=-1.0, beta=0.0, Cout=sim.err)
-        sim.com.add_(sim.err, alpha=float(sup.gain))
+    def _measure(self):
+        self.measure()
 
 
 # ------------------------------------------------------------------------------------------------ command line
-def _le_strehl(sup, nframes):
-    """long-exposure Strehl (mean over the environments) of `nframes` integrator frames behind a reset"""
-    sup.reset()
-    sup.next_part_one()
-    for _ in range(nframes):
-        sup.next_part_two(None, linear_control=True)
-        sup.next_part_one()
-    return float(sup.get_strehl()[:, 1].mean())
-
-
 def main(argv=None):
     import argparse
     from .env import VecRlSupervisor
@@ -549,11 +419,11 @@ def main(argv=None):
     a = ap.parse_args(argv)
     ps = P.load_param_file(a.config) if a.config.endswith(".py") and os.path.exists(a.config) else P.builtin(a.config)
     sup = VecRlSupervisor(ps, dict(n_reverse_filtered_from_cmat=a.nfilt), a.envs, device=a.device)
-    sr_sh = _le_strehl(sup, a.frames)
+    sr_sh = le_strehl(sup, a.frames)
     pyr = PyramidSensor(sup, nxsub=a.nxsub, pyr_ampl=a.ampl, pyr_npts=a.npts)
     pyr.calibrate()
     pyr.start()
-    sr_pyr = _le_strehl(sup, a.frames)
+    sr_pyr = le_strehl(sup, a.frames)
     pyr.stop()
     print("config %s, %d environments, %d frames, gain %g, %d modes filtered" % (ps.simul_name, a.envs, a.frames, sup.gain,
                                                                                 a.nfilt))

@@ -15,7 +15,7 @@ y, then shifted by (dx, dy) pupil pixels: A = (1 / G) [[cos, sin], [-sin, cos]],
 
 `trace_model` is that rule in NumPy (float64: the definition; float32: the yardstick of the device's round-off);
 `DmRegistration` holds the table of a VecRlSupervisor's simulator (csrc/aomarl_capi_dmreg.hip: k_trace_reg) and, between
-start() and stop(), gives VecRlSupervisor.next_part_one a branch of its own.
+start() and stop(), gives VecRlSupervisor.next_part_one its frame (attachments.py: the "registration" row).
 
     python -m ao_marl_amd.registration <config>      long-exposure Strehl against the shift, nominal and recalibrated
 """
@@ -23,6 +23,10 @@ import ctypes as C
 import os
 
 import numpy as np
+
+from . import attachments
+from .attachments import le_strehl
+from .loop_sensor import host_rows, through_mirrors
 
 ROW = 6
 A_MAX, DET_MIN, DET_MAX, T_DIMS = 4.0, 0.25, 4.0, 4.0       # csrc/aomarl_dmreg_host.h
@@ -191,6 +195,8 @@ class DmRegistration(object):
         ... sup.next_part_one(); sup.next_part_two(...) or VecAoEnv.step (the call-by-call path) ...
         reg.stop()
     """
+    slot = "registration"
+    row = attachments.TABLE[slot]
 
     def __init__(self, sup):
         self.sup = sup
@@ -294,7 +300,6 @@ class DmRegistration(object):
         noise-free image and slopes from the phase buffer, with the rows of `env` on all environments meanwhile; then
         modal.cmat_with_btt with the supervisor's filtered-mode count.  Leaves the table and the mirrors as they were
         (the mirrors on the loop's voltages); installs nothing (install_cmat does)."""
-        import torch
         from . import modal
         sup, sim = self.sup, self.sup.sim
         if self.native is None:
@@ -303,21 +308,16 @@ class DmRegistration(object):
             raise IndexError("DmRegistration.calibrate: environment %r of %d" % (env, self.nenv))
         m2v = np.asarray(sup.modes2volts, dtype=np.float64)             # [nactu][nmodes]
         v2m = np.asarray(sup.volts2modes, dtype=np.float64)             # [nmodes][nactu]
-        nm = m2v.shape[1]
         keep = self.rows.copy()
         for k in range(self.ndm):
             self.native.set_rows(k, np.tile(keep[k, int(env)], (self.nenv, 1)))
+
+        def read(n):
+            self.native.trace(False, atm=False, dms=True, reset=True)
+            sim.comp_image(from_phase_buffer=True, noise=False, write_bincube=False, cog=True)
+            return host_rows(sim.slopes, n)
         try:
-            resp = np.zeros((2, nm, sup.s.nslope))
-            for si, sign in enumerate((1.0, -1.0)):
-                for k0 in range(0, nm, sim.nenv):
-                    n = min(sim.nenv, nm - k0)
-                    v = torch.zeros(sim.nenv, m2v.shape[0], dtype=torch.float32, device=sim.device)
-                    v[:n] = torch.from_numpy(np.ascontiguousarray(sign * push_um * m2v[:, k0:k0 + n].T, dtype=np.float32)).to(sim.device)
-                    sim.comp_dm_shape(v)
-                    self.native.trace(False, atm=False, dms=True, reset=True)
-                    sim.comp_image(from_phase_buffer=True, noise=False, write_bincube=False, cog=True)
-                    resp[si, k0:k0 + n] = sim.slopes[:n].double().cpu().numpy()
+            resp = [through_mirrors(sim, sign * push_um * m2v.T, read) for sign in (1.0, -1.0)]
         finally:
             for k in range(self.ndm):
                 self.native.set_rows(k, keep[k])
@@ -330,38 +330,34 @@ class DmRegistration(object):
     # ---- the loop
     def start(self):
         """Attach: the supervisor's next_part_one traces through this table (see VecRlSupervisor.next_part_one)."""
-        sup, who = self.sup, "DmRegistration.start"
-        sim = sup.sim
-        if getattr(sup, "registration", None) is not None:
-            raise RuntimeError(who + ": the supervisor has a registration attached already")
-        if getattr(sim, "_twin", None) is not None:
-            raise RuntimeError(who + ": the frame pipeline is on (its frame kernel samples registered mirrors); build "
-                               "the environment with frame_pipeline=False")
-        if getattr(sup, "reset_prefetch", None) is not None:
-            raise RuntimeError(who + ": a prefetched reset is set (reset_prefetch): not covered")
-        if getattr(sup, "pure_delay_0", False):
-            raise NotImplementedError(who + ": modification_online (the pure-delay-0 call order) is not covered")
-        if getattr(sup, "geo", None) is not None:
-            raise RuntimeError(who + ": the GEO twin (geo=True) traces registered mirrors of its own: not covered")
-        if getattr(sup, "pyramid", None) is not None:
-            raise RuntimeError(who + ": a pyramid is attached (PyramidSensor.stop first)")
-        if getattr(sup, "lgs", None) is not None:
-            raise RuntimeError(who + ": a laser guide star is attached (LgsSensor.stop first)")
-        if getattr(sup, "autoencoder", None) is not None:
-            raise RuntimeError(who + ": the denoiser (autoencoder) path is not covered")
-        if getattr(sup, "keep_tar_image", False) or getattr(sup, "keep_le_image", False):
-            raise RuntimeError(who + ": keep_tar_image / keep_le_image: the full-frame target image traces for itself, "
-                                     "through registered mirrors")
-        sup.materialize_control()
-        sup.registration, self._attached = self, True
+        attachments.attach(self.sup, self.slot, self)
+        self._attached = True
         return self
 
     def stop(self):
-        if not self._attached:
-            return
-        if getattr(self.sup, "registration", None) is self:
-            self.sup.registration = None
-        self._attached = False
+        if self._attached:
+            attachments.detach(self.sup, self.slot, self)
+            self._attached = False
+
+    def frame(self, move_atmos):
+        """The frame of next_part_one behind the move: the unfused frame with both traces through the table (target
+        trace and PSF, sensor trace and image, the next move's prefetch).  Returns whether it kept the frame's phase
+        copy."""
+        sup, sim = self.sup, self.sup.sim
+        self.trace(target=True)
+        sim.target_psf_buffer()
+        self.trace(target=False)
+        sim.comp_image(from_phase_buffer=True, noise=True, write_bincube=False, cog=True)
+        kept = bool(sup.keep_wfs_phase)
+        if kept:                                # the buffer holds the registered phase the sensor just saw
+            sup._keep_wfs_phase_buffer()
+        if sup.prefetch_atmos and move_atmos:
+            sim.prefetch_atmos()
+        return kept
+
+    def control(self):
+        """The supervisor's own do_control, on its own command matrix (it also feeds an attached control law)."""
+        self.sup.sim.do_control()
 
 
 def install_cmat(sup, cmat):
@@ -375,16 +371,6 @@ def install_cmat(sup, cmat):
 
 
 # ------------------------------------------------------------------------------------------------ command line
-def _le_strehl(sup, nframes):
-    """long-exposure Strehl (mean over the environments) of `nframes` integrator frames behind a reset"""
-    sup.reset()
-    sup.next_part_one()
-    for _ in range(nframes):
-        sup.next_part_two(None, linear_control=True)
-        sup.next_part_one()
-    return float(sup.get_strehl()[:, 1].mean())
-
-
 def main(argv=None):
     import argparse
     from . import params as P
@@ -413,9 +399,9 @@ def main(argv=None):
         recal = reg.calibrate(env=0)
         reg.start()
         install_cmat(sup, nominal)
-        sr_nom = _le_strehl(sup, a.frames)                  # (the same seeds every row: reset() restarts them)
+        sr_nom = le_strehl(sup, a.frames)                  # (the same seeds every row: reset() restarts them)
         install_cmat(sup, recal)
-        sr_cal = _le_strehl(sup, a.frames)
+        sr_cal = le_strehl(sup, a.frames)
         reg.stop()
         print("%8.1f        %10.4f             %10.4f" % (shift, sr_nom, sr_cal))
     install_cmat(sup, nominal)

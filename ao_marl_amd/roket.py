@@ -10,6 +10,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import attachments
 from . import libaomarl as la
 
 # the order of the reference's covariance table (cov_cor, :445-453), with the key names of save_in_hdf5 (:402-410)
@@ -115,6 +116,13 @@ class RoketBank(object):
 
 
 # ---------------------------------------------------------------------------------------------- the breakdown
+_REFUSED = ("frame_pipeline", ("screens_ahead", "the breakdown would trace the NEXT frame's atmosphere (geo=True builds "
+                                                "it that way)"), "reset_prefetch",
+            ("env_gains", "the loop filter gRD is one matrix for all environments"),
+            ("modal_gains", "the loop filter gRD assumes the scalar integrator law"), "pure_delay_0",
+            ("autoencoder", "the breakdown of a denoised sensor is not covered", NotImplementedError))
+
+
 def _roket_supervisor(env):
     """The supervisor the breakdown runs on; refuses, naming the argument, every configuration in which the frame
     the loop measured is not the one its screens and mirrors stand on, or that the breakdown has no branch for."""
@@ -124,31 +132,11 @@ def _roket_supervisor(env):
     if getattr(env, "frame_pipeline", False) is not False:
         raise RuntimeError("VecRoket: the pipelined call order (frame_pipeline=%r) images frames one step ahead of "
                            "the chains; build the environment with frame_pipeline=False" % (env.frame_pipeline,))
-    sim = sup.sim
-    if getattr(sim, "_twin", None) is not None:
-        raise RuntimeError("VecRoket: the frame pipeline is enabled on this simulator; build the environment with "
-                           "frame_pipeline=False")
-    if sup.prefetch_atmos or getattr(sim, "prefetch", False) or getattr(sim, "pending_atmos", False):
-        raise RuntimeError("VecRoket: the screens run one frame ahead (prefetch_atmos): the breakdown would trace the "
-                           "NEXT frame's atmosphere; build the environment with prefetch_atmos=False (geo=True does)")
-    if getattr(sup, "reset_prefetch", None) is not None:
-        raise RuntimeError("VecRoket: a prefetched reset (reset_prefetch=%r) is not supported" % (sup.reset_prefetch,))
-    if sup.gain is None or getattr(sup, "_env_gains", False):
-        raise RuntimeError("VecRoket: per-environment gains (set_env_gains) are not supported: the loop filter gRD is "
-                           "one matrix for all environments")
-    if getattr(sup, "modal_gains", None) is not None:
-        raise RuntimeError("VecRoket: modal gains (set_modal_gains) are not supported: the loop filter gRD assumes the "
-                           "scalar integrator law; clear them with set_modal_gains(None)")
+    # (every attachment that senses: the breakdown's mirrors and its loop filter, gRD, are the Shack-Hartmann loop's)
+    attachments.refuse(sup, "VecRoket", _REFUSED, [s for s, r in attachments.TABLE.items() if r.senses])
     if sup.geo is None:
         raise RuntimeError("VecRoket: the fitting term and B come from the geometric twin; build the environment "
                            "with geo=True")
-    if getattr(sup, "registration", None) is not None:
-        raise RuntimeError("VecRoket: a mirror mis-registration is attached (DmRegistration.stop first): the breakdown's "
-                           "mirrors are the registered ones")
-    if sup.pure_delay_0:
-        raise NotImplementedError("VecRoket: modification_online (the pure-delay-0 call order) is not covered")
-    if sup.autoencoder is not None:
-        raise NotImplementedError("VecRoket: autoencoder: the breakdown of a denoised sensor is not covered")
     cfg = sup.config
     w, t = cfg.p_wfss[0], cfg.p_targets[0]
     if str(w.type).lower() != "sh":
