@@ -1037,3 +1037,4 @@ static DevState dev_state(const aomarl_state *st) {
 #include "aomarl_capi_composites.hip"
 #include "aomarl_capi_dmreg.hip"
 #include "aomarl_lgs.hip"
+#include "aomarl_tomo.hip"

@@ -13,7 +13,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 # AOMARL_LIB: another build of the same library (A/B measurements of kernel variants, csrc/Makefile `variant`)
 LIB_PATH = os.environ.get("AOMARL_LIB") or os.path.join(HERE, "libaomarl_hip.so")
-MAX_LAYERS, MAX_DMS, ABI_VERSION = 8, 4, 4
+MAX_LAYERS, MAX_DMS, ABI_VERSION = 8, 4, 5
 PRECISION_F32, PRECISION_SPLIT_F16 = 0, 1
 
 DM_PZT, DM_TT = 0, 1
@@ -213,6 +213,8 @@ SYMBOLS = [
     ("aomarl_lgs_set_ref", _i, [_vp, _fp]),
     ("aomarl_lgs_trace", _i, [_vp, _vp, C.POINTER(State), _fp, _i, _i, _i, _i, _vp]),
     ("aomarl_lgs_measure", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("aomarl_tomo_trace", _i, [_vp, C.POINTER(State), _vp, _vp, _i, _i, _i, _vp]),
+    ("aomarl_tomo_cov", _i, [_vp, _vp, _vp]),
     ("aomarl_groot_create", _i, [_vp, C.POINTER(C.c_void_p)]),
     ("aomarl_groot_destroy", _i, [_vp]),
     ("aomarl_groot_form", _i, [_vp, _vp, _vp, _vp, _i, _vp, _i, C.c_longlong, _vp]),
@@ -379,6 +381,17 @@ class GrootFormDesc(C.Structure):
     """aomarl_groot_form_desc (include/aomarl.h)"""
     _fields_ = [(n, C.c_int32) for n in ("model", "batch", "nlayers", "npts")] + [("x0", C.c_double)] + \
                [(n, _dp) for n in ("w", "sx", "sy", "L0")]
+
+
+class TomoDesc(C.Structure):
+    """aomarl_tomo_desc (include/aomarl.h)"""
+    _fields_ = [("nstars", C.c_int32), ("nlayers", C.c_int32), ("off", _fp), ("dm1", _fp)]
+
+
+class TomoCovDesc(C.Structure):
+    """aomarl_tomo_cov_desc (include/aomarl.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("n_row", "n_col", "k_row", "k_col", "nlayers")] + [("d", C.c_double)] + \
+               [(n, _dp) for n in ("row_px", "row_py", "col_px", "col_py", "row_stars", "col_stars", "layers")]
 
 
 def dptr(a):

@@ -26,7 +26,7 @@ extern "C" {
 
 #define AOMARL_MAX_LAYERS 8
 #define AOMARL_MAX_DMS 4
-#define AOMARL_ABI_VERSION 4
+#define AOMARL_ABI_VERSION 5
 
 enum { AOMARL_DM_PZT = 0, AOMARL_DM_TT = 1 };
 
@@ -1181,6 +1181,42 @@ int aomarl_lgs_trace(aomarl_lgs *p, aomarl_ctx *ctx, aomarl_state *st, const flo
  * are split into calls.  Asynchronous on `stream`; no allocation, no read-back. */
 int aomarl_lgs_measure(aomarl_lgs *p, const float *phase, int env_begin, int env_count, int flags, const uint32_t *seeds,
                        uint32_t *frame, float *image, float *slopes, void *stream);
+
+/* Laser tomography: a constellation of up to AOMARL_TOMO_MAX_STARS guide stars on the Shack-Hartmann sensor (DESIGN.md,
+ * "Laser tomography"; the model is ao_marl_amd/tomography.py: tomo_trace_model and slope_covariance).  The reference has
+ * the host wiring alone (shesha/ao/tomo.py); its covariances live in an external library that is not in its tree. */
+#define AOMARL_TOMO_MAX_STARS 8
+typedef struct {
+  int32_t nstars, nlayers;
+  const float *off;   /* HOST [nstars][nlayers][2]: the layer offset (x, y) of star k, wfs offset + theta_k alt_l / pupixsize */
+  const float *dm1;   /* HOST [nstars][nlayers]: delta_kl - 1 = -alt_l / gsalt_k, in (-1, 0] */
+} aomarl_tomo_desc;
+/* aomarl_lgs_trace for every star of an environment in one launch: pixel (x, y) of the sensor's grid samples layer l for
+ * star k at ((x, y) + off_kl) + dm1_kl ((x, y) - (n - 1) / 2), one fused multiply-add per coordinate, bilinear by the
+ * trace's rule; the mirrors (all in the pupil: the same value for every star) are evaluated once per pixel and added to
+ * each star's sum in controller order.  planes: DEVICE [nenv][nstars][n * n]; plane (e, k) has the bits aomarl_lgs_trace
+ * gives with star k's numbers.  flags: AOMARL_TRACE_ATMOS | _DMS | _RESET | _MASK.  Refused by name: nstars outside 1..8,
+ * a layer count that differs from the context's, non-finite offsets, dm1 outside (-1, 0], a footprint (the coordinate at
+ * the grid's corners) outside [0, dim - 1] of a screen, a null pointer, a bad range, a pipelined frame or a prefetched
+ * reset in flight.  Asynchronous on `stream`; no synchronisation, read-back or allocation. */
+int aomarl_tomo_trace(aomarl_ctx *ctx, aomarl_state *st, const aomarl_tomo_desc *desc, float *planes, int env_begin,
+                      int env_count, int flags, void *stream);
+/* The covariance in arcsec^2 of two-point slopes between directions (tomography.slope_covariance), in double:
+ *   out[(2 a + e) n_row + i][(2 b + f) n_col + j] = sum_l w_l sum_{s, s' = +-1} (-s s' / 2)
+ *       rodconan(|u_i^{a,l} - u_j^{b,l} + s delta_al d / 2 e - s' delta_bl d / 2 f|, L0_l),
+ *   u_i^{a,l} = delta_al p_i + alt_l theta_a,  delta_al = 1 - alt_l / gsalt_a,  theta in radians (arcsec 2 pi / 1296000),
+ *   w_l = (1e-6 206265 / d)^2 r0_l^(-5/3) (0.5 / 2 pi)^2;  layers outer, then the taps (+,+), (+,-), (-,+), (-,-).
+ * Every array of the desc is a HOST array, copied by the call: points in metres, stars [k][3] = (x arcsec, y arcsec,
+ * gsalt m; infinity: a natural star), layers [nlayers][3] = (alt m, r0_l m, L0_l m).  out: DEVICE double
+ * [2 n_row k_row][2 n_col k_col].  One thread per element, no atomics: the bits do not depend on the launch.  Allocates
+ * and frees its tables and synchronises `stream` (a calibration call). */
+typedef struct {
+  int32_t n_row, n_col, k_row, k_col, nlayers;
+  double d;                                   /* side of a sub-aperture in metres */
+  const double *row_px, *row_py, *col_px, *col_py;
+  const double *row_stars, *col_stars, *layers;
+} aomarl_tomo_cov_desc;
+int aomarl_tomo_cov(const aomarl_tomo_cov_desc *desc, double *out, void *stream);
 
 #ifdef __cplusplus
 }
