@@ -848,6 +848,9 @@ class HipSim(object):
         commands = np.ascontiguousarray(commands, dtype=np.float32)
         K = commands.shape[0]
         out = np.zeros((K, self.s.nslope), dtype=np.float32)
+        # the image kernel traces the mirrors itself only where every offset of the sensor's path is an integer (an
+        # off-axis guide star: fractional layer offsets); otherwise through the phase buffer
+        direct = all(float(o).is_integer() for t in (list(self.s.wfs_atm_off) + list(self.s.wfs_dm_off)) for o in t)
         for k0 in range(0, K, self.nenv):
             n = min(self.nenv, K - k0)
             v = torch.from_numpy(commands[k0:k0 + n]).to(self.device)
@@ -856,8 +859,10 @@ class HipSim(object):
                 self.raytrace_wfs(atm=False, dms=True, reset=True, env_begin=0, env_count=n)
                 self.slopes_geom(0, n)
             else:
-                self.comp_image(noise=False, cog=True, atm=False, dms=True, env_begin=0,
-                                env_count=n)
+                if not direct:
+                    self.raytrace_wfs(atm=False, dms=True, reset=True, env_begin=0, env_count=n)
+                self.comp_image(from_phase_buffer=not direct, noise=False, cog=True, atm=False, dms=True,
+                                env_begin=0, env_count=n)
             out[k0:k0 + n] = self.slopes[:n].cpu().numpy()
         return out
 

@@ -45,6 +45,21 @@ def calibrated(name="production_sh_10x10_2m", nfilt=5, hw=8):
     return copy.deepcopy(_calibrated(name, nfilt, hw))
 
 
+_BY_PARAMS = {}
+
+
+def calibrated_params(key, make_params, nfilt=5, hw=8):
+    """calibrated() for a system that is no built-in: `make_params()` returns its ParamSet, `key` names it (one
+    oracle-backed calibration per key and session).  (sysm, SimArrays, Calibration), deep-copied."""
+    k = (key, nfilt, hw)
+    if k not in _BY_PARAMS:
+        sysm = G.build_system(make_params())
+        s = system.from_system(sysm, strehl_halfwin=hw)
+        cal = modal.calibrate(s, sysm, OracleBackend(s), nfilt=nfilt)
+        _BY_PARAMS[k] = (sysm, s, cal)
+    return copy.deepcopy(_BY_PARAMS[k])
+
+
 def uncalibrated(name="production_sh_10x10_2m", hw=8):
     sysm = G.build_system(params.builtin(name))
     return sysm, system.from_system(sysm, strehl_halfwin=hw)

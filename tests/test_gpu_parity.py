@@ -9,6 +9,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from tests import helpers  # noqa: E402
+from tests import parity_stages as stages  # noqa: E402
 from oracle import aoref  # noqa: E402
 
 NAME = "production_sh_10x10_2m"
@@ -26,16 +27,7 @@ def setup():
     return sysm, s, cal, sim, oracles
 
 
-def _push_oracle_state(sim, oracles):
-    """Copy the oracle's screens into the HIP state (origin 0) so later stages are compared on
-    identical inputs."""
-    s = sim.s
-    for l, d in enumerate(s.screen_dim):
-        sim.set_screen(l, np.stack([o.screens[l] for o in oracles]))
-    for e, o in enumerate(oracles):
-        sim.t["ext_count"][e] = torch.tensor(o.ext_count, dtype=torch.int32)
-        sim.accumx[e] = o.accumx
-        sim.accumy[e] = o.accumy
+_push_oracle_state = stages.push_oracle_state
 
 
 def test_gemm_nt_matches_torch(setup):
@@ -56,12 +48,7 @@ def test_gemm_nt_matches_torch(setup):
 
 def test_reset_screens_match_oracle(setup):
     _, s, _, sim, oracles = setup
-    for l in range(s.nscreens):
-        scr = sim.screen(l).cpu().numpy()
-        for e, o in enumerate(oracles):
-            d = np.abs(scr[e] - o.screens[l]).max()
-            assert d < 2e-4, (l, e, d)   # 2n extrusions of fp32 recursion, screens ~ +-2 um
-            assert np.std(o.screens[l]) > 0.05
+    stages.check_reset_screens(sim, oracles)
 
 
 def test_reset_variants_give_the_same_screens(setup):
@@ -90,19 +77,7 @@ def test_reset_variants_give_the_same_screens(setup):
 
 def test_move_atmos_matches_oracle(setup):
     _, s, _, sim, oracles = setup
-    _push_oracle_state(sim, oracles)
-    for _ in range(7):
-        sim.move_atmos()
-        for o in oracles:
-            o.move_atmos()
-    for l in range(s.nscreens):
-        scr = sim.screen(l).cpu().numpy()
-        for e, o in enumerate(oracles):
-            assert np.abs(scr[e] - o.screens[l]).max() < 2e-5
-    # the ring origin moved, the logical content did not wrap
-    assert int(sim.t["origin"].abs().sum()) > 0
-    assert np.array_equal(sim.accumx[0], oracles[0].accumx)
-    assert np.array_equal(sim.accumy[0], oracles[0].accumy)
+    stages.check_moves(sim, oracles, nmoves=7)
 
 
 def test_all_four_extrusion_directions(setup):
@@ -131,16 +106,7 @@ def test_dm_shape_matches_oracle(setup, generic):
     """Both stack-array kernels: the separable-lattice fast path and the generic gather over the
     reference's influpos tables."""
     _, s, _, sim, oracles = setup
-    rng = np.random.default_rng(3)
-    volts = rng.normal(0, 1.0, size=(len(oracles), s.nactu)).astype(np.float32)
-    sim.set_option("force_generic_dm", generic)
-    sim.comp_dm_shape(torch.from_numpy(volts).cuda())
-    sim.set_option("force_generic_dm", 0)
-    for e, o in enumerate(oracles):
-        o.comp_shapes(volts[e])
-        for k in range(len(s.dms)):
-            a = sim.dm_shape(k)[e].cpu().numpy()
-            assert np.abs(a - o.dm_shapes[k]).max() < 2e-6 * max(1.0, np.abs(o.dm_shapes[k]).max())
+    stages.check_dm_shape(sim, oracles, generic)
 
 
 @pytest.mark.parametrize("generic", [0, 1])
@@ -148,44 +114,7 @@ def test_raytrace_and_spot_image_match_oracle(setup, generic):
     """Unfused API (raytrace -> buffer -> image), fused kernels (software-pipelined fast variant
     and the generic one), standalone COG."""
     _, s, _, sim, oracles = setup
-    sim.set_option("force_generic_spot", generic)
-    _push_oracle_state(sim, oracles)
-    rng = np.random.default_rng(4)
-    volts = rng.normal(0, 0.5, size=(len(oracles), s.nactu)).astype(np.float32)
-    sim.comp_dm_shape(torch.from_numpy(volts).cuda())
-    # unfused API: raytrace -> phase buffer -> image from buffer
-    sim.raytrace_wfs(atm=True, dms=False, reset=True)
-    sim.raytrace_wfs(atm=False, dms=True, reset=False)
-    sim.comp_image(from_phase_buffer=True, noise=False, write_bincube=True, cog=True)
-    cube_buf = sim.t["bincube"].cpu().numpy().copy()
-    sl_buf = sim.slopes.cpu().numpy().copy()
-    ph = sim.t["wfs_phase"].cpu().numpy()
-    # fused path
-    sim.comp_image(from_phase_buffer=False, noise=False, write_bincube=True, cog=True)
-    cube_fused = sim.t["bincube"].cpu().numpy().copy()
-    sl_fused = sim.slopes.cpu().numpy().copy()
-    sim.do_centroids()
-    sl_cog = sim.slopes.cpu().numpy().copy()
-    # slopes-only path (no bincube): single-pass reduction of the raw image
-    sim.comp_image(from_phase_buffer=False, noise=False, write_bincube=False, cog=True)
-    sl_only = sim.slopes.cpu().numpy().copy()
-    sim.set_option("force_generic_spot", 0)
-    for e, o in enumerate(oracles):
-        o.comp_shapes(volts[e])
-        o.raytrace_wfs(atm=True, dms=False, reset=True)
-        o.raytrace_wfs(atm=False, dms=True, reset=False)
-        assert np.abs(ph[e] - o.wfs_phase).max() < 1e-5
-        o.comp_image(noise=False)
-        o.do_centroids()
-        scale = o.bincube.max()
-        assert np.abs(cube_buf[e] - o.bincube).max() < 2e-5 * scale
-        assert np.abs(cube_fused[e] - o.bincube).max() < 2e-5 * scale
-        # "bit-exact centroid indices": brightest pixel of every spot
-        assert np.array_equal(cube_fused[e].argmax(axis=1), o.bincube.argmax(axis=1))
-        assert np.allclose(cube_fused[e].sum(axis=1), s.nphot * s.flux, rtol=1e-5)
-        for sl in (sl_buf, sl_fused, sl_cog, sl_only):
-            assert np.abs(sl[e] - o.slopes).max() < 1e-4   # arcsec (north-star tolerance)
-        assert np.abs(sl_fused[e] - o.slopes).max() < 2e-5
+    stages.check_raytrace_and_spots(sim, oracles, generic)
 
 
 def test_control_chain_matches_oracle(setup):
@@ -249,96 +178,14 @@ def test_rl_control_matches_numpy(setup):
 def test_target_psf_and_strehl_match_oracle(setup, valu):
     """All three PSF-row kernels: software-pipelined MFMA (0), VALU fallback (1), generic MFMA (2)."""
     _, s, _, sim, oracles = setup
-    sim.set_option("force_valu_target", 1 if valu == 1 else 0)
-    sim.set_option("force_generic_target", 1 if valu == 2 else 0)
-    _push_oracle_state(sim, oracles)
-    rng = np.random.default_rng(7)
-    volts = rng.normal(0, 0.3, size=(len(oracles), s.nactu)).astype(np.float32)
-    sim.comp_dm_shape(torch.from_numpy(volts).cuda())
-    sim.reset_strehl()
-    for rep in range(2):
-        sim.target_psf()
-        sim.comp_strehl()
-    sim.raytrace_target()
-    tp = sim.t["tar_phase"].cpu().numpy()
-    st = sim.strehl.cpu().numpy()
-    for e, o in enumerate(oracles):
-        o.comp_shapes(volts[e])
-        o.reset_strehl()
-        o.raytrace_target()
-        assert np.abs(tp[e] - o.tar_phase).max() < 1e-5
-        for rep in range(2):
-            want = o.comp_strehl()
-        assert abs(st[e, 0] - want[0]) < 2e-5 * max(want[0], 1e-3) + 1e-7
-        assert abs(st[e, 1] - want[1]) < 2e-5 * max(want[1], 1e-3) + 1e-7
-        assert abs(st[e, 2] - want[2]) < 1e-4 * want[2] + 1e-9
-        assert abs(st[e, 3] - want[3]) < 1e-4 * want[3] + 1e-9
-        # comp_strehl(do_fit=True), the reference's default: the peaks fitted by two 1-D sincs (oracle: the same
-        # algorithm in double precision on its own window)
-        fit, sf = o.get_strehl(do_fit=True), sim.strehl_fit.cpu().numpy()
-        assert fit[0] >= want[0] and fit[1] >= want[1] and fit[0] < 1.2 * want[0] + 1e-6
-        assert abs(sf[e, 0] - fit[0]) < 1e-4 * max(fit[0], 1e-3) + 1e-7, (sf[e], fit)
-        assert abs(sf[e, 1] - fit[1]) < 1e-4 * max(fit[1], 1e-3) + 1e-7, (sf[e], fit)
-    sim.set_option("force_valu_target", 0)
-    sim.set_option("force_generic_target", 0)
+    stages.check_target_psf(sim, oracles, valu)
 
 
 def test_fused_frame_matches_oracle_and_unfused(setup):
     """One-pass frame kernel (science PSF rows + WFS spots from the same phase tiles) vs the
     oracle and vs the separate target / WFS kernels, with and without the bincube."""
     _, s, _, sim, oracles = setup
-    assert sim.frame_fused_available()
-    _push_oracle_state(sim, oracles)
-    rng = np.random.default_rng(11)
-    volts = rng.normal(0, 0.4, size=(len(oracles), s.nactu)).astype(np.float32)
-    volts[:, -2:] = rng.normal(0, 0.05, size=(len(oracles), 2))      # tip-tilt: analytic planes
-    sim.comp_dm_shape(torch.from_numpy(volts).cuda())
-    out = {}
-    for mode in ("unfused", "fused_cube", "fused", "otf_cube", "otf", "otf_f32"):
-        sim.reset_strehl()
-        sim.set_option("force_f32_dft", 1 if mode == "otf_f32" else 0)
-        if mode.startswith("otf"):
-            # stack-array DM evaluated from st.voltage inside the kernel: the stored planes are
-            # poisoned to prove they are not read
-            assert sim.dm_from_voltage_available()
-            sim.set_com(torch.from_numpy(volts).cuda())
-            sim.apply_control(comp_voltage=False, defer_shape=True)
-            nz = s.dms[0].dim ** 2
-            sim.t["dm_shape"][:, :nz] = 1e3
-            assert sim._stale
-        if mode == "unfused":
-            sim.target_psf()
-            sim.comp_image(noise=False, write_bincube=True, cog=True)
-        else:
-            sim.t["bincube"].zero_()
-            sim.slopes.zero_()
-            sim.frame_fused(noise=False, write_bincube=mode.endswith("cube"), cog=True)
-        sim.comp_strehl()
-        out[mode] = (sim.slopes.cpu().numpy().copy(), sim.strehl.cpu().numpy().copy(),
-                     sim.t["bincube"].cpu().numpy().copy())
-    sim.set_option("force_f32_dft", -1)         # back to the library's precision mode
-    # materialising afterwards restores the stored planes from the same voltages
-    shp = sim.dm_shape(0).cpu().numpy()
-    assert not sim._stale
-    for e, o in enumerate(oracles):
-        o.comp_shapes(volts[e])
-        o.reset_strehl()
-        o.raytrace_target()
-        want = o.comp_strehl()
-        o.raytrace_wfs(atm=True, dms=True, reset=True)
-        o.comp_image(noise=False)
-        o.do_centroids()
-        assert np.abs(shp[e].ravel() - o.dm_shapes[0].ravel()).max() < 2e-6 * max(1.0, np.abs(o.dm_shapes[0]).max())
-        for mode in ("fused_cube", "fused", "otf_cube", "otf", "otf_f32"):
-            sl, st, cube = out[mode]
-            assert np.abs(sl[e] - o.slopes).max() < 2e-5, mode
-            assert np.abs(sl[e] - out["unfused"][0][e]).max() < 2e-5, mode
-            assert abs(st[e, 0] - want[0]) < 2e-5 * max(want[0], 1e-3) + 1e-7, mode
-            assert abs(st[e, 2] - want[2]) < 1e-4 * want[2] + 1e-9, mode
-        for mode in ("fused_cube", "otf_cube"):
-            cube = out[mode][2]
-            assert np.abs(cube[e] - o.bincube).max() < 2e-5 * o.bincube.max(), mode
-            assert np.array_equal(cube[e].argmax(axis=1), o.bincube.argmax(axis=1)), mode
+    stages.check_fused_frame(sim, oracles)
 
 
 @pytest.mark.parametrize("unfused", [0, 1, 2, 3])
@@ -348,40 +195,9 @@ def test_closed_loop_trace_matches_oracle(setup, unfused):
     -- DFTs and internal GEMMs on split-fp16 MFMAs -- (0), separate target / WFS passes (1), the
     one-pass kernel reading materialised DM shapes (2), the one-pass kernel as the product runs it by
     default: everything fp32 (3).  1 - 3 in the default precision (f32)."""
-    from ao_marl_amd import libaomarl as la
     _, s, _, sim, oracles = setup
-    keep_precision = la.get_precision()
-    la.set_precision("split_f16" if unfused == 0 else "f32")
-    la.arith_launches(reset=True)
-    sim.set_option("force_unfused_frame", 1 if unfused == 1 else 0)
-    sim.set_option("force_f32_dft", -1)
-    sim.defer_shape = unfused in (0, 3)
-    sim.reset(SEEDS)
-    for o, sd in zip(oracles, SEEDS):
-        o.reset(sd)
-    _push_oracle_state(sim, oracles)   # remove the reset's accumulated round-off
-    sim.target_psf()
-    for o in oracles:
-        o.raytrace_target()
-    worst = 0.0
-    for it in range(40):
-        sim.next_part_two(None)
-        sim.next_part_one()
-        sl = sim.slopes.cpu().numpy()
-        cm = sim.com.cpu().numpy()
-        st = sim.strehl.cpu().numpy()
-        for e, o in enumerate(oracles):
-            o.next_part_two(None)
-            o.next_part_one()
-            worst = max(worst, np.abs(sl[e] - o.slopes).max())
-            assert np.abs(sl[e] - o.slopes).max() < 1e-4, it
-            assert np.abs(cm[e] - o.com).max() < 5e-5 * np.abs(o.com).max() + 1e-3, it
-            assert abs(st[e, 0] - o.strehl_se) < 1e-4, it
-            assert abs(st[e, 1] - o.strehl_le) < 1e-4, it
-    sim.set_option("force_unfused_frame", 0)
-    sim.defer_shape = True
-    launched = {k: v for k, v in la.arith_launches().items() if v}
-    la.set_precision(keep_precision)
+    launched, worst, _ = stages.closed_loop(sim, oracles, SEEDS, "split_f16" if unfused == 0 else "f32",
+                                            unfused=unfused == 1, defer_shape=unfused in (0, 3))
     if unfused == 0:
         assert launched.get("frame_kernel_dft:split_f16_mfma") == 40 and launched.get("gemm:split_f16_mfma", 0) > 0
     else:
