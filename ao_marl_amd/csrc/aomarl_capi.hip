@@ -1038,3 +1038,4 @@ static DevState dev_state(const aomarl_state *st) {
 #include "aomarl_capi_dmreg.hip"
 #include "aomarl_lgs.hip"
 #include "aomarl_tomo.hip"
+#include "aomarl_field.hip"

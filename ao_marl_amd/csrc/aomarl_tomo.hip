@@ -19,8 +19,9 @@ struct TomoArgs {
   float dm1[AOMARL_MAX_LAYERS][AOMARL_TOMO_MAX_STARS];
 };
 
-// trace_dms<false>'s values one by one: vals[k] is what mirror k adds at pixel (x, y); bit k of the result: it adds
-// (the pixel lies on the mirror).  Expression for expression trace_dms's.
+// trace_dms<TARGET>'s values one by one: vals[k] is what mirror k adds at pixel (x, y); bit k of the result: it adds
+// (the pixel lies on the mirror).  Expression for expression trace_dms's.  (TARGET: the science field, aomarl_field.hip.)
+template <bool TARGET = false>
 __device__ __forceinline__ unsigned trace_dm_values(const DevSys &sys, const DevState &st, int e, int x, int y,
                                                     float (&vals)[AOMARL_MAX_DMS]) {
   unsigned has = 0;
@@ -29,7 +30,7 @@ __device__ __forceinline__ unsigned trace_dm_values(const DevSys &sys, const Dev
     vals[k] = 0.f;
     if (k < sys.ndm) {
       const DevDm &D = sys.dms[k];
-      const float fx = (float)x + D.wxo, fy = (float)y + D.wyo;
+      const float fx = (float)x + (TARGET ? D.txo : D.wxo), fy = (float)y + (TARGET ? D.tyo : D.wyo);
       const int ix = (int)floorf(fx), iy = (int)floorf(fy);
       if (ix >= 0 && iy >= 0 && ix < D.dim && iy < D.dim) {
         const float wx = fx - (float)ix, wy = fy - (float)iy;

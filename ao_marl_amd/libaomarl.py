@@ -215,6 +215,12 @@ SYMBOLS = [
     ("aomarl_lgs_measure", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     ("aomarl_tomo_trace", _i, [_vp, C.POINTER(State), _vp, _vp, _i, _i, _i, _vp]),
     ("aomarl_tomo_cov", _i, [_vp, _vp, _vp]),
+    ("aomarl_field_create", _i, [_vp, _i, _vp, C.POINTER(C.c_void_p)]),
+    ("aomarl_field_destroy", _i, [_vp]),
+    ("aomarl_field_observe", _i, [_vp, _vp, C.POINTER(State), _i, _i, _i, _vp]),
+    ("aomarl_field_trace", _i, [_vp, _vp, C.POINTER(State), _vp, _i, _i, _i, _vp]),
+    ("aomarl_field_reset", _i, [_vp, _i, _i, _vp]),
+    ("aomarl_field_get", _i, [_vp, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _vp]),
     ("aomarl_groot_create", _i, [_vp, C.POINTER(C.c_void_p)]),
     ("aomarl_groot_destroy", _i, [_vp]),
     ("aomarl_groot_form", _i, [_vp, _vp, _vp, _vp, _i, _vp, _i, C.c_longlong, _vp]),
@@ -392,6 +398,11 @@ class TomoCovDesc(C.Structure):
     """aomarl_tomo_cov_desc (include/aomarl.h)"""
     _fields_ = [(n, C.c_int32) for n in ("n_row", "n_col", "k_row", "k_col", "nlayers")] + [("d", C.c_double)] + \
                [(n, _dp) for n in ("row_px", "row_py", "col_px", "col_py", "row_stars", "col_stars", "layers")]
+
+
+class FieldDesc(C.Structure):
+    """aomarl_field_desc (include/aomarl.h)"""
+    _fields_ = [("ndir", C.c_int32), ("nlayers", C.c_int32), ("off", _fp), ("inv_lambda", C.c_float)]
 
 
 def dptr(a):

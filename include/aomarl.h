@@ -1218,6 +1218,48 @@ typedef struct {
 } aomarl_tomo_cov_desc;
 int aomarl_tomo_cov(const aomarl_tomo_cov_desc *desc, double *out, void *stream);
 
+/* Science field: Strehl and long-exposure PSF window in any number of directions per environment ("Science
+ * field"; the model is ao_marl_amd/field.py: field_offsets, field_trace_model, FieldModel).  Natural stars: no cone.
+ * The mirrors all sit in the pupil and are traced by the target's rule: their value at a pixel is the same for every
+ * direction.  The PSF grid (npsf, strehl_halfwin, ref_peak) is the context's; one wavelength per object. */
+#define AOMARL_FIELD_MAX_DIRS 16 /* directions per launch; a field with more runs as consecutive launches */
+typedef struct {
+  int32_t ndir, nlayers;
+  const float *off;  /* HOST [ndir][nlayers][2]: the layer offset (x, y) of direction d on the pupil (pupdiam) grid,
+                        the target's offset + theta_d alt_l / pupixsize; copied by aomarl_field_create */
+  float inv_lambda;  /* 1 / wavelength in microns */
+} aomarl_field_desc;
+typedef struct aomarl_field aomarl_field;
+/* The object owns record [nenv][ndir][8] (the slots of aomarl_state.strehl, per direction), le [nenv][ndir][W][W]
+ * (W = 2 strehl_halfwin, the long-exposure sum) and its workspaces; everything is allocated here, zeroed.  Refused by
+ * name: ndir < 1, a layer count that differs from the context's, non-finite offsets, a footprint (the coordinate at the
+ * pupil grid's corners) outside [0, dim - 1] of a screen, a mirror that is not in the pupil (at altitude), null
+ * pointers, nenv < 1, nenv ndir pupdiam^2 beyond 2^31 - 1, inv_lambda non-finite or <= 0. */
+int aomarl_field_create(aomarl_ctx *ctx, int nenv, const aomarl_field_desc *desc, aomarl_field **out);
+int aomarl_field_destroy(aomarl_field *f);
+/* For every environment of the range and every direction: the phase of the state as it stands, traced bilinearly by the
+ * trace's rule through the layers (flags & AOMARL_TRACE_ATMOS) and the mirrors (AOMARL_TRACE_DMS), straight into the
+ * windowed PSF |DFT_npsf(spupil exp(2 pi i phase inv_lambda))|^2 on [-hw, hw)^2, the phase variance over the lit pixels
+ * and the sinc fit; committed into the object's record and long-exposure sum (what aomarl_comp_strehl does to
+ * st->strehl / st->le_img).  No phase plane is written; st->tar_phase, st->strehl, st->le_img and the pending PSF slot
+ * are not touched; deferred stack-array shapes are materialised first (aomarl_target_image).  No atomics, every sum in
+ * a fixed order: the record and the window of direction d of environment e have the same bits however the environments
+ * are split into calls, however many other directions the field has and whichever launch d falls into.  Refused by
+ * name: null pointers, a state of another size, a bad range, unknown flags, a pipelined frame or a prefetched reset in
+ * flight.  Asynchronous on `stream`; no synchronisation, read-back or allocation. */
+int aomarl_field_observe(aomarl_field *f, aomarl_ctx *ctx, aomarl_state *st, int env_begin, int env_count, int flags,
+                         void *stream);
+/* The traced planes alone: planes DEVICE [nenv][ndir][pupdiam^2], flags AOMARL_TRACE_ATMOS | _DMS | _RESET | _MASK as
+ * for aomarl_tomo_trace (_MASK multiplies by spupil).  Direction offsets that are whole pixels give
+ * aomarl_raytrace_target's bits. */
+int aomarl_field_trace(aomarl_field *f, aomarl_ctx *ctx, aomarl_state *st, float *planes, int env_begin, int env_count,
+                       int flags, void *stream);
+/* Zero the record and the long-exposure sum of the environments of the range. */
+int aomarl_field_reset(aomarl_field *f, int env_begin, int env_count, void *stream);
+/* Device pointers to record and le (either may be NULL); do_fit: first solve the long exposure's sinc fit into slot 7
+ * of every record (on demand, like aomarl_strehl_fit), asynchronously on `stream`. */
+int aomarl_field_get(aomarl_field *f, int do_fit, float **record, float **le, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
