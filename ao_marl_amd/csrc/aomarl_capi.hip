@@ -1039,3 +1039,4 @@ static DevState dev_state(const aomarl_state *st) {
 #include "aomarl_lgs.hip"
 #include "aomarl_tomo.hip"
 #include "aomarl_field.hip"
+#include "aomarl_mcao.hip"

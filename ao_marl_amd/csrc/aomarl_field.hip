@@ -3,11 +3,12 @@
 // unit, like aomarl_tomo.hip: the trace reads the context's static description and the state, the PSF finish reuses
 // psf_window_fit, fit_axis_gain and strehl_commit_body on the field's own buffers.  The host half is aomarl_field_host.h.
 #include "aomarl_field_host.h"
+#include "aomarl_mcao_sample.h"
 
 // Everything below is compiled without floating-point contraction: where a multiply-add is fused it is written as one
 // (__builtin_fmaf).  The kernels exist in several instantiations (the direction count is a template argument) and a
 // direction must come out with the same bits from each; left to the compiler, which products are fused with which sums
-// differs between instantiations.  (This file is the last one of the translation unit.)
+// differs between instantiations.  (Only aomarl_mcao.hip follows in the translation unit; it sets the pragma itself.)
 #pragma clang fp contract(off)
 
 // bilinear_ring with the operations spelled out: zero outside the screen, the last line clamped; weights of zero give
@@ -33,6 +34,11 @@ struct aomarl_field {
   float *TR = nullptr;                 // [nenv][chunk][pupdiam][W][2]: stage 1 of the launch's directions
   float *TPART = nullptr;              // [nenv][chunk][nblk][4]: (sum d, sum d^2, lit pixels, -) per row block
   float *PEND = nullptr;               // [nenv][ndir][W W + 4]: window, variance, fitted gain
+  // mirrors at altitude (aomarl_field_attach_mirrors, aomarl_mcao.hip): the object whose planes the directions see, and
+  // the directions' offsets on them, HOST [ndir][nmirrors][2]; null: none
+  const struct aomarl_mcao *mir = nullptr;
+  std::vector<float> mir_off;
+  FieldMirArgs mir_base = {};          // planes, nmirrors, stride, dim of the attached object (no offsets)
 };
 
 // =============================================================================================
@@ -43,11 +49,14 @@ struct aomarl_field {
 // next power of two KT >= K; the slots past K have zero offsets (a read inside the screens) and their sums are never
 // stored.  Each mirror is evaluated once per pixel by the target's rule (trace_dm_values<true>: trace_dms<true>'s
 // expression) and added to every direction in controller order, after the layers.  Per direction the operations and their
-// order do not depend on K, KT or the other directions.
+// order do not depend on K, KT or the other directions.  ALT: behind the pupil mirrors, the attached object's mirrors at
+// altitude per direction, in mirror order, by k_mcao_add's sampling function (mcao_bilinear) with dm1 = 0; without ALT the
+// text is what it was.
 // =============================================================================================
-template <int KT>
+template <int KT, bool ALT = false>
 __device__ __forceinline__ void field_pixel(const DevSys &sys, const DevState &st, const FieldArgs &a, int e, int x, int y,
-                                            int flags, float (&v)[KT]) {
+                                            int flags, float (&v)[KT],
+                                            const typename FieldMir<ALT>::type &ma = typename FieldMir<ALT>::type()) {
   if (flags & AOMARL_TRACE_ATMOS) {
     for (int l = 0; l < sys.nlayers; l++) {
       const DevLayer &L = sys.layers[l];
@@ -67,6 +76,17 @@ __device__ __forceinline__ void field_pixel(const DevSys &sys, const DevState &s
         for (int k = 0; k < KT; k++) v[k] += dmv[m];
       }
   }
+  if constexpr (ALT) {
+    if (flags & AOMARL_TRACE_DMS) {
+#pragma unroll
+      for (int m = 0; m < FIELD_MAX_ALT; m++)
+        if (m < ma.nmirrors) {
+          const float *pl = ma.planes + ((long long)e * ma.nmirrors + m) * ma.stride;
+#pragma unroll
+          for (int k = 0; k < KT; k++) v[k] += mcao_bilinear(pl, ma.dim[m], (float)x + ma.ox[m][k], (float)y + ma.oy[m][k]);
+        }
+    }
+  }
 }
 
 // =============================================================================================
@@ -81,10 +101,10 @@ __device__ __forceinline__ void field_pixel(const DevSys &sys, const DevState &s
 // LDS is dynamic: [KT][256] float2 amplitudes (reused by the reduction) | [256] counts | [Npsf] float2 twiddles when
 // Npsf <= FIELD_TW_LDS (at most 49 KiB with 16 directions).  W is even (2 hw).
 // =============================================================================================
-template <int KT>
-__global__ __launch_bounds__(FIELD_THREADS) void k_field_rows(DevSys sys, DevState st, FieldArgs a, int K, int chunk,
-                                                              float inv_lambda, int env_begin, int flags,
-                                                              float *__restrict__ TR, float *__restrict__ TPART, int nblk) {
+template <int KT, bool ALT>
+__device__ __forceinline__ void field_rows_body(DevSys sys, DevState st, FieldArgs a, int K, int chunk, float inv_lambda,
+                                                int env_begin, int flags, float *__restrict__ TR, float *__restrict__ TPART,
+                                                int nblk, typename FieldMir<ALT>::type ma) {
   extern __shared__ __attribute__((aligned(16))) float fsm[];
   const int W = 2 * sys.hw, RB = FIELD_THREADS / W, pd = sys.pupdiam, np = sys.npsf;
   float2 *samp = reinterpret_cast<float2 *>(fsm);                       // [KT][256]
@@ -101,7 +121,7 @@ __global__ __launch_bounds__(FIELD_THREADS) void k_field_rows(DevSys sys, DevSta
   float pivot[KT];
 #pragma unroll
   for (int k = 0; k < KT; k++) pivot[k] = 0.f;
-  field_pixel<KT>(sys, st, a, e, pd / 2, pd / 2, flags, pivot);
+  field_pixel<KT, ALT>(sys, st, a, e, pd / 2, pd / 2, flags, pivot, ma);
   // the chunk's pixel of this thread, and its output element
   const int py = tid / W, px = tid - py * W;           // (py < RB: the threads past RB W idle in the trace)
   const int kxi = px, ys = py, kxf = kxi - sys.hw;
@@ -119,7 +139,7 @@ __global__ __launch_bounds__(FIELD_THREADS) void k_field_rows(DevSys sys, DevSta
 #pragma unroll
       for (int k = 0; k < KT; k++) v[k] = 0.f;
       if (m != 0.f) {
-        field_pixel<KT>(sys, st, a, e, x, y, flags, v);
+        field_pixel<KT, ALT>(sys, st, a, e, x, y, flags, v, ma);
         sm += 1.f;
       }
 #pragma unroll
@@ -192,6 +212,21 @@ __global__ __launch_bounds__(FIELD_THREADS) void k_field_rows(DevSys sys, DevSta
   }
 }
 
+// the kernel as it was, and the one that sees mirrors at altitude (its FieldMirArgs behind the other arguments)
+template <int KT>
+__global__ __launch_bounds__(FIELD_THREADS) void k_field_rows(DevSys sys, DevState st, FieldArgs a, int K, int chunk,
+                                                              float inv_lambda, int env_begin, int flags,
+                                                              float *__restrict__ TR, float *__restrict__ TPART, int nblk) {
+  field_rows_body<KT, false>(sys, st, a, K, chunk, inv_lambda, env_begin, flags, TR, TPART, nblk, FieldNoMirrors());
+}
+template <int KT>
+__global__ __launch_bounds__(FIELD_THREADS) void k_field_rows_alt(DevSys sys, DevState st, FieldArgs a, int K, int chunk,
+                                                                  float inv_lambda, int env_begin, int flags,
+                                                                  float *__restrict__ TR, float *__restrict__ TPART, int nblk,
+                                                                  FieldMirArgs ma) {
+  field_rows_body<KT, true>(sys, st, a, K, chunk, inv_lambda, env_begin, flags, TR, TPART, nblk, ma);
+}
+
 // =============================================================================================
 // k_field_finish: one workgroup per (direction of the launch, environment).  k_target_finish on the field's buffers --
 // stage 2 G[ky][kx] = sum_y R[y][kx] exp(-2 pi i ky y / Npsf) in double, |G|^2 into the direction's pending window, the short
@@ -237,9 +272,10 @@ __global__ __launch_bounds__(256) void k_field_finish(DevSys sys, DevState fst, 
 }
 
 // the traced planes alone (tests, users of the off-axis phase): k_tomo_trace's shape on the pupil grid
-template <int KT>
-__global__ __launch_bounds__(256) void k_field_trace(DevSys sys, DevState st, FieldArgs a, int K, int ndir, int first,
-                                                     float *__restrict__ planes, int env_begin, int flags) {
+template <int KT, bool ALT>
+__device__ __forceinline__ void field_trace_body(DevSys sys, DevState st, FieldArgs a, int K, int ndir, int first,
+                                                 float *__restrict__ planes, int env_begin, int flags,
+                                                 typename FieldMir<ALT>::type ma) {
   const int pd = sys.pupdiam;
   const int e = env_begin + blockIdx.y;
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -249,11 +285,22 @@ __global__ __launch_bounds__(256) void k_field_trace(DevSys sys, DevState st, Fi
   float v[KT];
 #pragma unroll
   for (int k = 0; k < KT; k++) v[k] = (k < K && !(flags & AOMARL_TRACE_RESET)) ? out[(long long)k * pd * pd] : 0.f;
-  field_pixel<KT>(sys, st, a, e, x, y, flags, v);
+  field_pixel<KT, ALT>(sys, st, a, e, x, y, flags, v, ma);
   const float mk = (flags & AOMARL_TRACE_MASK) ? sys.spupil[p] : 1.f;
 #pragma unroll
   for (int k = 0; k < KT; k++)
     if (k < K) out[(long long)k * pd * pd] = (flags & AOMARL_TRACE_MASK) ? v[k] * mk : v[k];
+}
+
+template <int KT>
+__global__ __launch_bounds__(256) void k_field_trace(DevSys sys, DevState st, FieldArgs a, int K, int ndir, int first,
+                                                     float *__restrict__ planes, int env_begin, int flags) {
+  field_trace_body<KT, false>(sys, st, a, K, ndir, first, planes, env_begin, flags, FieldNoMirrors());
+}
+template <int KT>
+__global__ __launch_bounds__(256) void k_field_trace_alt(DevSys sys, DevState st, FieldArgs a, int K, int ndir, int first,
+                                                         float *__restrict__ planes, int env_begin, int flags, FieldMirArgs ma) {
+  field_trace_body<KT, true>(sys, st, a, K, ndir, first, planes, env_begin, flags, ma);
 }
 
 // the instantiation of a launch of K directions: the next power of two
@@ -344,8 +391,17 @@ int aomarl_field_observe(aomarl_field *f, aomarl_ctx *c, aomarl_state *st, int b
 #define FIELD_ROWS(KT)                                                                                                          \
   hipLaunchKernelGGL(k_field_rows<KT>, dim3(f->nblk, n), dim3(FIELD_THREADS), sm, s, sy, ds, a, L.count, f->chunk, f->inv_lambda, b, \
                      flags, f->TR, f->TPART, f->nblk)
-    FIELD_DISPATCH(L.count, FIELD_ROWS);
+#define FIELD_ROWS_ALT(KT)                                                                                                      \
+  hipLaunchKernelGGL(k_field_rows_alt<KT>, dim3(f->nblk, n), dim3(FIELD_THREADS), sm, s, sy, ds, a, L.count, f->chunk,        \
+                     f->inv_lambda, b, flags, f->TR, f->TPART, f->nblk, ma)
+    if (f->mir) {
+      const FieldMirArgs ma = field_mir_args(f->mir_base, f->mir_off.data(), L);
+      FIELD_DISPATCH(L.count, FIELD_ROWS_ALT);
+    } else {
+      FIELD_DISPATCH(L.count, FIELD_ROWS);
+    }
 #undef FIELD_ROWS
+#undef FIELD_ROWS_ALT
     LAUNCHCHK();
     hipLaunchKernelGGL(k_field_finish, dim3(L.count, n), dim3(256), 0, s, sy, fst, f->ndir, L.first, f->chunk, b, f->TR, f->TPART,
                        f->nblk, f->PEND);
@@ -366,8 +422,17 @@ int aomarl_field_trace(aomarl_field *f, aomarl_ctx *c, aomarl_state *st, float *
 #define FIELD_TRACE(KT)                                                                                                          \
   hipLaunchKernelGGL(k_field_trace<KT>, dim3((np + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, traced_sys(c), dev_state(st), a, \
                      L.count, f->ndir, L.first, planes, b, flags)
-    FIELD_DISPATCH(L.count, FIELD_TRACE);
+#define FIELD_TRACE_ALT(KT)                                                                                                      \
+  hipLaunchKernelGGL(k_field_trace_alt<KT>, dim3((np + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, traced_sys(c),       \
+                     dev_state(st), a, L.count, f->ndir, L.first, planes, b, flags, ma)
+    if (f->mir) {
+      const FieldMirArgs ma = field_mir_args(f->mir_base, f->mir_off.data(), L);
+      FIELD_DISPATCH(L.count, FIELD_TRACE_ALT);
+    } else {
+      FIELD_DISPATCH(L.count, FIELD_TRACE);
+    }
 #undef FIELD_TRACE
+#undef FIELD_TRACE_ALT
     LAUNCHCHK();
   }
   return 0;

@@ -112,3 +112,29 @@ static inline FieldArgs field_args(const float *off, int nlayers, const FieldLau
     }
   return a;
 }
+
+// ---- mirrors at altitude attached to the field (aomarl_field_attach_mirrors; the view's validation is
+// mcao_validate_attach, aomarl_mcao_host.h).  The ALT instantiations of the kernels take a FieldMirArgs behind their other
+// arguments, the others an empty struct: planes [nenv][nmirrors][stride] of the attached object, mirror m's plane of side
+// dim[m], the offsets [mirror][direction of the launch] (dm1 = 0: natural stars).
+#define FIELD_MAX_ALT 2              // (AOMARL_MCAO_MAX_MIRRORS)
+struct FieldNoMirrors {};
+struct FieldMirArgs {
+  const float *planes;
+  int nmirrors, stride, dim[FIELD_MAX_ALT];
+  float ox[FIELD_MAX_ALT][AOMARL_FIELD_MAX_DIRS], oy[FIELD_MAX_ALT][AOMARL_FIELD_MAX_DIRS];
+};
+template <bool ALT> struct FieldMir { typedef FieldNoMirrors type; };
+template <> struct FieldMir<true> { typedef FieldMirArgs type; };
+// base: planes, nmirrors, stride, dim filled in; off: HOST [ndir][nmirrors][2]
+static inline FieldMirArgs field_mir_args(const FieldMirArgs &base, const float *off, const FieldLaunch &L) {
+  FieldMirArgs a = base;
+  memset(a.ox, 0, sizeof(a.ox));
+  memset(a.oy, 0, sizeof(a.oy));
+  for (int m = 0; m < base.nmirrors; m++)
+    for (int k = 0; k < L.count; k++) {
+      a.ox[m][k] = off[2 * ((size_t)(L.first + k) * base.nmirrors + m)];
+      a.oy[m][k] = off[2 * ((size_t)(L.first + k) * base.nmirrors + m) + 1];
+    }
+  return a;
+}

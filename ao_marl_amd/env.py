@@ -328,6 +328,8 @@ class VecRlSupervisor(object):
             self.autoencoder.check_range()      # a saturated fp16 launch of the last episode is an error
         self.check_range()
         self.sim.reset(self.env_seeds())
+        if getattr(self.sensing, "reset", None) is not None:
+            self.sensing.reset()                # state the attachment owns (multi-conjugate AO: its mirrors at altitude)
         if self.control_law is not None:
             self.control_law.restart()          # its history starts over; what it has learned carries across episodes
         self._atmos_changed_behind = None
@@ -460,6 +462,8 @@ class VecRlSupervisor(object):
             # (... and never under an attachment whose trace reads the planes)
             self.sim.apply_control(defer_shape=getattr(self.sim, "defer_shape", False) and not self.pure_delay_0 and
                                    not (self.sensing is not None and self.sensing.row.reads_planes))
+            if getattr(self.sensing, "apply", None) is not None:
+                self.sensing.apply()            # mirrors the attachment owns (multi-conjugate AO): their delay line and shapes
             if self.pure_delay_0:
                 self.sim.target_psf()           # raytrace_target behind apply_control (rlSupervisor.py:938-939)
         if snap and self.pure_delay_0:

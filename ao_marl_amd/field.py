@@ -329,6 +329,16 @@ class NativeField(object):
         n = self.nenv - env_begin if env_count is None else int(env_count)
         la.check(self.lib.aomarl_field_reset(self.handle, int(env_begin), n, self._stream()))
 
+    def attach_mirrors(self, native_mcao, off, dm1):
+        """the field sees the mirrors at altitude of `native_mcao` (mcao.NativeMcao) from now on: off [T][M][2], dm1 [T][M]"""
+        v = native_mcao.view(off, dm1)
+        la.check(self.lib.aomarl_field_attach_mirrors(self.handle, native_mcao.handle, C.byref(v[0])))
+        self._mirrors = native_mcao                     # (kept alive: the field reads its planes)
+
+    def detach_mirrors(self):
+        la.check(self.lib.aomarl_field_detach_mirrors(self.handle))
+        self._mirrors = None
+
     def fit(self):
         """the long exposure's fit into slot 7 of every record"""
         la.check(self.lib.aomarl_field_get(self.handle, 1, None, None, self._stream()))
@@ -343,9 +353,11 @@ class ScienceField(object):
         fld.strehl()                                    # [nenv][T][4]: SE, LE, phase variance, its mean (get_strehl's)
 
     observe() looks at the state as it stands (module docstring); it only reads the simulator.  On a CPU simulator with one
-    oracle per environment (`sim.sims`) it runs FieldModel."""
+    oracle per environment (`sim.sims`) it runs FieldModel.  mirrors: a mcao.MultiConjugate whose mirrors at altitude every
+    direction sees through its own footprint (behind the pupil mirrors); while one is attached to the supervisor, a field
+    without it refuses to observe."""
 
-    def __init__(self, sup_or_sim, directions, Lambda=None, sysm=None):
+    def __init__(self, sup_or_sim, directions, Lambda=None, sysm=None, mirrors=None):
         self.sup = sup_or_sim if hasattr(sup_or_sim, "sim") else None
         self.sim = self.sup.sim if self.sup is not None else sup_or_sim
         sysm = sysm if sysm is not None else getattr(sup_or_sim, "sysm", None)
@@ -362,6 +374,13 @@ class ScienceField(object):
         if not self.Lambda > 0 or not np.isfinite(self.Lambda):
             raise ValueError("field: Lambda = %r microns must be positive and finite" % (Lambda,))
         self.off = field_offsets(sysm, self.directions)
+        self.mirrors, self.mir_view = mirrors, None
+        if mirrors is not None:
+            from .mcao import mirror_offsets
+            owner = mirrors.sup.sim if getattr(mirrors, "sup", None) is not None else getattr(mirrors, "sim", None)
+            if owner is not self.sim:
+                raise ValueError("ScienceField: mirrors is a MultiConjugate (or a NativeMcao) on another simulator")
+            self.mir_view = mirror_offsets(sysm, mirrors.mirrors, self.directions, "pupil")
         self.device = str(self.sim.device)
         self.W, self.pd = 2 * int(s.strehl_halfwin), int(s.pupdiam)
         if self.device == "cpu":
@@ -371,6 +390,8 @@ class ScienceField(object):
         else:
             self.native = NativeField(self.sim, self.off, self.Lambda)
             self.model = None
+            if mirrors is not None:
+                self.native.attach_mirrors(mirrors.mc, *self.mir_view)
 
     # ---- what the CPU path needs
     def _oracles(self):
@@ -380,13 +401,18 @@ class ScienceField(object):
                                       "(`sims`); field_trace_model is the NumPy statement")
         return sims
 
-    def _cpu_planes(self, o, atm=True, dms=True):
+    def _cpu_planes(self, e, atm=True, dms=True):
+        o = self._oracles()[e]
         pl = field_trace_model(o.screens, self.off, self.pd) if atm else np.zeros((self.T, self.pd, self.pd))
         if dms:
             keep = o.tar_phase.copy()                      # the oracle's own science phase is not ours to change
             o.raytrace_target(atm=False, dms=True, reset=True)
             pl = pl + np.asarray(o.tar_phase, dtype=np.float64)[None]
             o.tar_phase[:] = keep
+            if self.mirrors is not None:
+                from .mcao import mirrors_add_model
+                pl = mirrors_add_model(pl, [np.asarray(sh[e], dtype=np.float64) for sh in self.mirrors.alt_shapes()],
+                                       *self.mir_view)
         return pl
 
     def _range(self, env_begin, env_count):
@@ -397,6 +423,12 @@ class ScienceField(object):
 
     def _refuse_in_flight(self, who):
         sim = self.sim
+        att = getattr(self.sup, "lgs", None)
+        # (mirrors may be the attachment or the device object that owns its planes)
+        if getattr(att, "altitude_mirrors", False) and self.mirrors is not att and \
+                (self.mirrors is None or att.mc is None or getattr(self.mirrors, "mc", None) is not att.mc):
+            raise RuntimeError("%s: a MultiConjugate is attached: every direction sees its mirrors at altitude through "
+                               "its own footprint; build the field with mirrors=<the MultiConjugate> (or its field())" % who)
         if getattr(sim, "_twin", None) is not None and sim.frame_pipeline_state()[0]:
             raise RuntimeError("%s: a pipelined frame is in flight (the frames run a step ahead of the chains)" % who)
         pending = getattr(sim, "prefetch_reset_pending", None)
@@ -414,7 +446,7 @@ class ScienceField(object):
             return
         sims = self._oracles()
         for e in range(b, b + n):
-            self.model.observe(self._cpu_planes(sims[e]), self._record[e], self._le[e])
+            self.model.observe(self._cpu_planes(e), self._record[e], self._le[e])
 
     def trace(self, atm=True, dms=True, env_begin=0, env_count=None):
         """The traced planes [nenv][T][pupdiam][pupdiam] in microns (rows outside the range are zero)"""
@@ -427,7 +459,7 @@ class ScienceField(object):
         sims = self._oracles()
         out = np.zeros((self.nenv, self.T, self.pd, self.pd))
         for e in range(b, b + n):
-            out[e] = self._cpu_planes(sims[e], atm, dms)
+            out[e] = self._cpu_planes(e, atm, dms)
         return out
 
     def reset(self, env_begin=0, env_count=None):
@@ -475,10 +507,10 @@ class ScienceField(object):
 
 
 # ------------------------------------------------------------------------------------------------ command line
-def strehl_against_angle(sup, directions, nframes):
+def strehl_against_angle(sup, directions, nframes, mirrors=None):
     """long-exposure Strehl [T] (mean over the environments, fitted) of nframes of the loop as it is set up, behind a
-    reset, and the loop's own on-axis figure"""
-    fld = ScienceField(sup, directions)
+    reset, and the loop's own on-axis figure.  mirrors: the attached mcao.MultiConjugate, if one is"""
+    fld = ScienceField(sup, directions, mirrors=mirrors)
     sup.reset()
     st = fld.run(nframes)
     le = st[..., 1]

@@ -221,6 +221,14 @@ SYMBOLS = [
     ("aomarl_field_trace", _i, [_vp, _vp, C.POINTER(State), _vp, _i, _i, _i, _vp]),
     ("aomarl_field_reset", _i, [_vp, _i, _i, _vp]),
     ("aomarl_field_get", _i, [_vp, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _vp]),
+    ("aomarl_mcao_create", _i, [_vp, _i, _vp, C.POINTER(C.c_void_p)]),
+    ("aomarl_mcao_destroy", _i, [_vp]),
+    ("aomarl_mcao_com", _i, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("aomarl_mcao_apply", _i, [_vp, _vp, _i, _i, _vp, _vp]),
+    ("aomarl_mcao_reset", _i, [_vp, _i, _i, _vp]),
+    ("aomarl_mcao_add", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    ("aomarl_field_attach_mirrors", _i, [_vp, _vp, _vp]),
+    ("aomarl_field_detach_mirrors", _i, [_vp]),
     ("aomarl_groot_create", _i, [_vp, C.POINTER(C.c_void_p)]),
     ("aomarl_groot_destroy", _i, [_vp]),
     ("aomarl_groot_form", _i, [_vp, _vp, _vp, _vp, _i, _vp, _i, C.c_longlong, _vp]),
@@ -403,6 +411,25 @@ class TomoCovDesc(C.Structure):
 class FieldDesc(C.Structure):
     """aomarl_field_desc (include/aomarl.h)"""
     _fields_ = [("ndir", C.c_int32), ("nlayers", C.c_int32), ("off", _fp), ("inv_lambda", C.c_float)]
+
+
+MCAO_MAX_MIRRORS, MCAO_MAX_DIRS = 2, 8
+
+
+class McaoMirror(C.Structure):
+    """aomarl_mcao_mirror (include/aomarl.h)"""
+    _fields_ = [("alt", C.c_float)] + [(n, C.c_int32) for n in ("dim", "pitch", "i1min", "j1min", "gw", "gh", "ss", "nact")] + \
+               [("grid", _ip), ("prof", _fp)]
+
+
+class McaoDesc(C.Structure):
+    """aomarl_mcao_desc (include/aomarl.h)"""
+    _fields_ = [("nmirrors", C.c_int32), ("mirrors", McaoMirror * MCAO_MAX_MIRRORS)]
+
+
+class McaoView(C.Structure):
+    """aomarl_mcao_view (include/aomarl.h)"""
+    _fields_ = [("ndir", C.c_int32), ("off", _fp), ("dm1", _fp)]
 
 
 def dptr(a):

@@ -1260,6 +1260,69 @@ int aomarl_field_reset(aomarl_field *f, int env_begin, int env_count, void *stre
  * of every record (on demand, like aomarl_strehl_fit), asynchronously on `stream`. */
 int aomarl_field_get(aomarl_field *f, int do_fit, float **record, float **le, void *stream);
 
+/* Multi-conjugate AO: up to AOMARL_MCAO_MAX_MIRRORS stack-array mirrors conjugated to altitudes h_m >= 0, owned by the
+ * object and not by the context ("Multi-conjugate AO"; the model is ao_marl_amd/mcao.py: altitude_mirror,
+ * mirror_shape_model, mirror_offsets, mirrors_add_model, delay_line_model).  Every guide star and every science direction
+ * sees a mirror at altitude through its own footprint. */
+#define AOMARL_MCAO_MAX_MIRRORS 2
+#define AOMARL_MCAO_MAX_DIRS 8 /* directions (stars) per aomarl_mcao_add */
+typedef struct {
+  float alt;                    /* metres, >= 0 */
+  int32_t dim;                  /* the side of the mirror's plane in pupil pixels */
+  int32_t pitch, i1min, j1min;  /* the lattice: the patch of cell (gx, gy) starts at (i1min + pitch gx, j1min + pitch gy) */
+  int32_t gw, gh;               /* lattice cells */
+  int32_t ss, nact;             /* the profile's length; actuators */
+  const int32_t *grid;          /* HOST [gh][gw]: the cell's actuator, or -1 */
+  const float *prof;            /* HOST [ss]: the separable profile, influence(a, b) = prof[a] prof[b] microns per unit */
+} aomarl_mcao_mirror;
+typedef struct {
+  int32_t nmirrors;
+  aomarl_mcao_mirror mirrors[AOMARL_MCAO_MAX_MIRRORS];
+} aomarl_mcao_desc;
+/* How `ndir` directions look at the mirrors: pixel (x, y) of a grid of side nn samples mirror m for direction k at
+ * ((x, y) + off_km) + dm1_km ((x, y) - (nn - 1) / 2), one fused multiply-add per coordinate (aomarl_tomo_trace's layer
+ * rule), bilinear by the trace's rule for a plain plane: zero outside, the last line clamped. */
+typedef struct {
+  int32_t ndir;
+  const float *off; /* HOST [ndir][nmirrors][2] */
+  const float *dm1; /* HOST [ndir][nmirrors]: -h_m / gsalt_k in (-1, 0]; 0: a natural star, a science direction */
+} aomarl_mcao_view;
+typedef struct aomarl_mcao aomarl_mcao;
+/* The object owns com, com1, com2, voltage [nenv][nact_total] (the mirrors' actuators one after the other) and the planes
+ * [nenv][nmirrors][dim_max^2] (mirror m uses the first dim_m^2 floats of its slot, row length dim_m); all allocated here,
+ * zeroed.  Refused by name: nmirrors outside 1..2, alt negative or not finite, a lattice that leaves the plane, grid
+ * entries outside -1..nact - 1, a profile longer than the shape kernel's patch of lattice cells, null pointers, nenv < 1,
+ * planes beyond 2^31 - 1 elements. */
+int aomarl_mcao_create(aomarl_ctx *ctx, int nenv, const aomarl_mcao_desc *desc, aomarl_mcao **out);
+int aomarl_mcao_destroy(aomarl_mcao *m);
+/* Device pointers to the commands, the delayed voltages and the planes (each may be NULL). */
+int aomarl_mcao_com(aomarl_mcao *m, float **com, float **voltage, float **planes);
+/* volts == NULL: the delay line, voltage = wa com + wb com1 + wc com2 with the context's delay weights, com2 <- com1,
+ * com1 <- com (aomarl_apply_control's expression and order), then every mirror's plane from the voltages.  volts: DEVICE
+ * [env_count][nact_total], shaped directly (the calibration's pokes, like aomarl_comp_dm_shape); the delay line is not
+ * touched.  No atomics, every sum in a fixed order.  Asynchronous on `stream`. */
+int aomarl_mcao_apply(aomarl_mcao *m, aomarl_ctx *ctx, int env_begin, int env_count, const float *volts, void *stream);
+/* Zero the commands, the delay line, the voltages and the planes of the environments of the range. */
+int aomarl_mcao_reset(aomarl_mcao *m, int env_begin, int env_count, void *stream);
+/* planes[e][k] += sum_m sample(mirror m) for the ndir directions of the view, in mirror order, behind whatever the plane
+ * holds; planes: DEVICE [nenv][ndir][nn^2] with nn the context's n (the sensor's grid; what aomarl_tomo_trace left) or
+ * pupdiam (with ndir = 1: the state's tar_phase).  flags: AOMARL_TRACE_MASK multiplies the result by mpupil (nn = n) or
+ * spupil (nn = pupdiam).  Plane (e, k) has the same bits however many other directions the call has and however the
+ * environments are split into calls.  Refused by name: ndir outside 1..8 or different from the view's, nn neither n nor
+ * pupdiam, non-finite offsets, dm1 outside (-1, 0], a footprint (the coordinate at the grid's corners) outside
+ * [0, dim_m - 1], null pointers, a bad range, unknown flags, planes beyond 2^31 - 1 elements, a pipelined frame or a
+ * prefetched reset in flight.  Asynchronous on `stream`; no synchronisation, read-back or allocation. */
+int aomarl_mcao_add(aomarl_mcao *m, aomarl_ctx *ctx, const aomarl_mcao_view *view, float *planes, int ndir, int nn,
+                    int env_begin, int env_count, int flags, void *stream);
+/* The science field through the mirrors: from now on aomarl_field_observe and aomarl_field_trace add, under
+ * AOMARL_TRACE_DMS and behind the pupil mirrors, the planes of `m` as they stand, per direction, by aomarl_mcao_add's
+ * sampling with dm1 = 0 on the pupil grid.  view: one entry per direction of the field (copied).  The object `m` must
+ * outlive the attachment.  A field without attached mirrors runs what it ran before.  Refused by name: null pointers,
+ * environment counts that differ, a view whose direction count differs from the field's, dm1 != 0, non-finite offsets, a
+ * footprint outside [0, dim_m - 1]. */
+int aomarl_field_attach_mirrors(aomarl_field *f, aomarl_mcao *m, const aomarl_mcao_view *view);
+int aomarl_field_detach_mirrors(aomarl_field *f);
+
 #ifdef __cplusplus
 }
 #endif
