@@ -1,8 +1,12 @@
 // aomarl_capi.hip -- C ABI (include/aomarl.h) over the gfx950 kernels in aomarl_kernels.hip: context, create / destroy,
-// setters and options here; the entry points by concern in aomarl_capi_*.hip, included at the end (one translation unit).
+// setters and options here; the entry points by concern in aomarl_capi_atmos / _stages / _agents / _step / _extras /
+// _composites.hip, included at the end (one translation unit: the environment).  Mirror registration, the laser guide
+// star, tomography, the science field and the altitude mirrors are units of their own; what they may ask of a context is
+// defined at the very end (aomarl_env_host.h).
 // Host side only sequences kernel launches on the caller's stream; no device<->host copies after
 // aomarl_create / aomarl_set_* (aomarl_reset uploads env_count seeds, 4 bytes each).
 #include "aomarl_kernels.hip"
+#include "aomarl_env_host.h"
 #include "aomarl_qf4_host.h"
 #include "aomarl_step_plan_host.h"
 
@@ -1017,7 +1021,7 @@ static int check_range(const aomarl_ctx *c, const aomarl_state *st, int b, int n
   return 0;
 }
 
-static DevState dev_state(const aomarl_state *st) {
+DevState dev_state(const aomarl_state *st) {
   DevState d;
   d.nenv = st->nenv; d.ld_actu = st->ld_actu;
   d.screens = st->screens; d.origin = st->origin; d.seeds = st->seeds; d.ext_count = st->ext_count;
@@ -1035,8 +1039,51 @@ static DevState dev_state(const aomarl_state *st) {
 #include "aomarl_capi_step.hip"
 #include "aomarl_capi_extras.hip"
 #include "aomarl_capi_composites.hip"
-#include "aomarl_capi_dmreg.hip"
-#include "aomarl_lgs.hip"
-#include "aomarl_tomo.hip"
-#include "aomarl_field.hip"
-#include "aomarl_mcao.hip"
+
+// ---------------------------------------------------------------- the context as the sensing and field units see it
+// (aomarl_env_host.h; they are translation units of their own and never see struct aomarl_ctx)
+EnvView env_view(const aomarl_ctx *c) {
+  EnvView v;
+  v.sys = traced_sys(c);
+  v.nlayers = c->nlayers; v.ndm = c->ndm; v.delay = c->delay;
+  v.frac_x = c->subpixel_flow ? c->frac_x : nullptr;
+  v.frac_y = c->subpixel_flow ? c->frac_y : nullptr;
+  return v;
+}
+
+int env_busy(const aomarl_ctx *c) {
+  return (c->pipe.active ? ENV_PIPELINED : 0) | (c->rp && c->rp->n > 0 ? ENV_RESET_PREFETCHED : 0);
+}
+
+int env_refuse_busy(const char *who, const aomarl_ctx *c) {
+  const int busy = env_busy(c);
+  if (busy & ENV_PIPELINED) return fail("%s: the frame pipeline is on (the frames run a step ahead of the chains)", who);
+  if (busy & ENV_RESET_PREFETCHED) return fail("%s: a prefetched reset is in flight", who);
+  return 0;
+}
+
+int env_trace_ready(aomarl_ctx *c, aomarl_state *st, int b, int n, int flags, void *stream) {
+  int rc = check_range(c, st, b, n);
+  if (rc) return rc;
+  rc = atmos_wait_pending(c, stream);
+  if (rc) return rc;
+  if (n > 0 && c->defer_dm_shape && (flags & AOMARL_TRACE_DMS))   // the stack-array shapes exist only as voltages: form them
+    rc = dm_shape_impl(c, st, b, n, nullptr, false, stream);
+  return rc;
+}
+
+int launch_inc_u32(uint32_t *p, int n, hipStream_t s) {
+  hipLaunchKernelGGL(k_inc_u32, dim3((n + 255) / 256), dim3(256), 0, s, p, n);
+  LAUNCHCHK();
+  return 0;
+}
+int launch_strehl_reset(const DevSys &sys, const DevState &st, int env_begin, int n, hipStream_t s) {
+  hipLaunchKernelGGL(k_strehl_reset, dim3(n), dim3(256), 0, s, sys, st, env_begin);
+  LAUNCHCHK();
+  return 0;
+}
+int launch_strehl_fit_le(const DevSys &sys, const DevState &st, int env_begin, int n, hipStream_t s) {
+  hipLaunchKernelGGL(k_strehl_fit_le, dim3(n), dim3(64), 0, s, sys, st, env_begin);
+  LAUNCHCHK();
+  return 0;
+}

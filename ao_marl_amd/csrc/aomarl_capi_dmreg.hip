@@ -1,6 +1,8 @@
 // aomarl_capi_dmreg.hip -- mirror mis-registration per environment (include/aomarl.h: aomarl_dmreg_*; reference:
-// dmCompass.py:148-176).  Part of aomarl_capi.hip's translation unit: the trace reads the context's static description
-// and the state exactly as aomarl_raytrace_wfs / _target do.  The host half is aomarl_dmreg_host.h.
+// dmCompass.py:148-176).  A translation unit of its own: the trace reads the context's static description and the state
+// exactly as aomarl_raytrace_wfs / _target do, through aomarl_env_host.h.  The host half is aomarl_dmreg_host.h.
+#include "aomarl_env_host.h"
+#include "aomarl_trace_dev.h"
 #include "aomarl_dmreg_host.h"
 
 // =============================================================================================
@@ -97,7 +99,11 @@ struct aomarl_dmreg {
   float *table = nullptr;          // device [nenv][ndm][6]
 };
 
-static bool dmreg_reset_in_flight(const aomarl_ctx *c) { return c->rp && c->rp->n > 0; }
+// dmreg_validate_ctx on a context's busy bits: this unit's own wording of the two refusals
+static int dmreg_refuse_busy(const aomarl_ctx *c, const char *who, std::string &err) {
+  const int busy = env_busy(c);
+  return dmreg_validate_ctx(busy & ENV_PIPELINED, busy & ENV_RESET_PREFETCHED, who, err);
+}
 
 int aomarl_dmreg_destroy(aomarl_dmreg *r) {
   if (!r) return 0;
@@ -110,18 +116,19 @@ int aomarl_dmreg_create(aomarl_ctx *c, int nenv, aomarl_dmreg **out) {
   if (!c || !out) return fail("dmreg_create: null argument");
   *out = nullptr;
   std::string err;
-  if (dmreg_validate_create(nenv, c->ndm, err)) return fail("%s", err.c_str());
-  if (dmreg_validate_ctx(c->pipe.active, dmreg_reset_in_flight(c), "dmreg_create", err)) return fail("%s", err.c_str());
-  for (int k = 0; k < c->ndm; k++) {
-    const DevDm &D = c->sys.dms[k];
-    if (dmreg_validate_geometry(c->sys.n, D.wxo, D.wyo, D.dim, k, err) ||
-        dmreg_validate_geometry(c->sys.pupdiam, D.txo, D.tyo, D.dim, k, err))
+  const EnvView v = env_view(c);
+  if (dmreg_validate_create(nenv, v.ndm, err)) return fail("%s", err.c_str());
+  if (dmreg_refuse_busy(c, "dmreg_create", err)) return fail("%s", err.c_str());
+  for (int k = 0; k < v.ndm; k++) {
+    const DevDm &D = v.sys.dms[k];
+    if (dmreg_validate_geometry(v.sys.n, D.wxo, D.wyo, D.dim, k, err) ||
+        dmreg_validate_geometry(v.sys.pupdiam, D.txo, D.tyo, D.dim, k, err))
       return fail("%s", err.c_str());
   }
   aomarl_dmreg *r = new aomarl_dmreg();
-  r->owner = c; r->nenv = nenv; r->ndm = c->ndm;
-  for (int k = 0; k < c->ndm; k++) r->dim[k] = c->sys.dms[k].dim;
-  const size_t rows = (size_t)nenv * (size_t)c->ndm;
+  r->owner = c; r->nenv = nenv; r->ndm = v.ndm;
+  for (int k = 0; k < v.ndm; k++) r->dim[k] = v.sys.dms[k].dim;
+  const size_t rows = (size_t)nenv * (size_t)v.ndm;
   std::vector<float> ident(rows * DMREG_ROW);
   dmreg_identity(ident.data(), (long long)rows);
   hipError_t e = hipMalloc((void **)&r->table, sizeof(float) * rows * DMREG_ROW);
@@ -163,26 +170,21 @@ int aomarl_dmreg_trace(aomarl_dmreg *r, aomarl_ctx *c, aomarl_state *st, int b, 
   if (!r || !c || !st) return fail("dmreg_trace: null argument");
   if (r->owner != c) return fail("dmreg_trace: the table was created with another context");
   std::string err;
-  if (dmreg_validate_ctx(c->pipe.active, dmreg_reset_in_flight(c), "dmreg_trace", err)) return fail("%s", err.c_str());
+  if (dmreg_refuse_busy(c, "dmreg_trace", err)) return fail("%s", err.c_str());
   if (st->nenv != r->nenv) return fail("dmreg_trace: the table has %d environments, the state %d", r->nenv, st->nenv);
   const int known = AOMARL_TRACE_ATMOS | AOMARL_TRACE_DMS | AOMARL_TRACE_RESET | AOMARL_TRACE_MASK;
   if (dmreg_validate_trace(r->nenv, b, n, target, flags, known, err)) return fail("%s", err.c_str());
-  int rc = check_range(c, st, b, n);
-  if (rc) return rc;
-  rc = atmos_wait_pending(c, stream);
+  const int rc = env_trace_ready(c, st, b, n, flags, stream);
   if (rc) return rc;
   if (!(target ? st->tar_phase : st->wfs_phase)) return fail("dmreg_trace needs st->%s", target ? "tar_phase" : "wfs_phase");
   if (n == 0) return 0;
-  if (c->defer_dm_shape && (flags & AOMARL_TRACE_DMS)) {       // the stack-array shapes exist only as voltages: form them
-    rc = dm_shape_impl(c, st, b, n, nullptr, false, stream);
-    if (rc) return rc;
-  }
-  const int nn = target ? c->sys.pupdiam : c->sys.n;
+  const EnvView v = env_view(c);
+  const int nn = target ? v.sys.pupdiam : v.sys.n;
   const dim3 grid((nn * nn + TREG_THREADS - 1) / TREG_THREADS, n);
   if (target)
-    hipLaunchKernelGGL(k_trace_reg<true>, grid, dim3(TREG_THREADS), 0, (hipStream_t)stream, traced_sys(c), dev_state(st), r->table, b, flags);
+    hipLaunchKernelGGL(k_trace_reg<true>, grid, dim3(TREG_THREADS), 0, (hipStream_t)stream, v.sys, dev_state(st), r->table, b, flags);
   else
-    hipLaunchKernelGGL(k_trace_reg<false>, grid, dim3(TREG_THREADS), 0, (hipStream_t)stream, traced_sys(c), dev_state(st), r->table, b, flags);
+    hipLaunchKernelGGL(k_trace_reg<false>, grid, dim3(TREG_THREADS), 0, (hipStream_t)stream, v.sys, dev_state(st), r->table, b, flags);
   LAUNCHCHK();
   return 0;
 }

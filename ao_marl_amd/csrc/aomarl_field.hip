@@ -1,14 +1,17 @@
 // aomarl_field.hip -- the science field (include/aomarl.h: aomarl_field_*).  gfx950 only.
-// The model is ao_marl_amd/field.py (field_trace_model, FieldModel; float64 NumPy).  Part of aomarl_capi.hip's translation
-// unit, like aomarl_tomo.hip: the trace reads the context's static description and the state, the PSF finish reuses
-// psf_window_fit, fit_axis_gain and strehl_commit_body on the field's own buffers.  The host half is aomarl_field_host.h.
+// The model is ao_marl_amd/field.py (field_trace_model, FieldModel; float64 NumPy).  A translation unit of its own, like
+// aomarl_tomo.hip: the trace reads the context's static description and the state through aomarl_env_host.h, the PSF
+// finish reuses psf_window_fit, fit_axis_gain and strehl_commit_body (aomarl_trace_dev.h) on the field's own buffers.  The
+// host half is aomarl_field_host.h.
+#include "aomarl_env_host.h"
+#include "aomarl_trace_dev.h"
 #include "aomarl_field_host.h"
 #include "aomarl_mcao_sample.h"
 
 // Everything below is compiled without floating-point contraction: where a multiply-add is fused it is written as one
 // (__builtin_fmaf).  The kernels exist in several instantiations (the direction count is a template argument) and a
 // direction must come out with the same bits from each; left to the compiler, which products are fused with which sums
-// differs between instantiations.  (Only aomarl_mcao.hip follows in the translation unit; it sets the pragma itself.)
+// differs between instantiations.  (The headers above come first: the helpers they define keep the default contraction.)
 #pragma clang fp contract(off)
 
 // bilinear_ring with the operations spelled out: zero outside the screen, the last line clamped; weights of zero give
@@ -315,12 +318,12 @@ __global__ __launch_bounds__(256) void k_field_trace_alt(DevSys sys, DevState st
 static_assert(AOMARL_FIELD_MAX_DIRS == 16, "FIELD_DISPATCH covers 1..16 directions");
 
 // ------------------------------------------------------------------------------------------------- host side
-static FieldSys field_sys(const aomarl_ctx *c) {
+static FieldSys field_sys(const EnvView &v) {
   FieldSys sy;
   memset(&sy, 0, sizeof(sy));
-  sy.nlayers = c->nlayers; sy.pupdiam = c->sys.pupdiam; sy.hw = c->sys.hw; sy.ndm = c->ndm;
-  for (int l = 0; l < c->nlayers; l++) sy.dims[l] = c->sys.layers[l].dim;
-  for (int k = 0; k < c->ndm; k++) { sy.dm_dim[k] = c->sys.dms[k].dim; sy.dm_txo[k] = c->sys.dms[k].txo; sy.dm_tyo[k] = c->sys.dms[k].tyo; }
+  sy.nlayers = v.nlayers; sy.pupdiam = v.sys.pupdiam; sy.hw = v.sys.hw; sy.ndm = v.ndm;
+  for (int l = 0; l < v.nlayers; l++) sy.dims[l] = v.sys.layers[l].dim;
+  for (int k = 0; k < v.ndm; k++) { sy.dm_dim[k] = v.sys.dms[k].dim; sy.dm_txo[k] = v.sys.dms[k].txo; sy.dm_tyo[k] = v.sys.dms[k].tyo; }
   return sy;
 }
 
@@ -334,11 +337,12 @@ int aomarl_field_destroy(aomarl_field *f) {
 
 int aomarl_field_create(aomarl_ctx *c, int nenv, const aomarl_field_desc *d, aomarl_field **out) {
   if (!c) return fail("field_create: null ctx");
+  const EnvView v = env_view(c);
   std::string err;
-  if (field_validate_desc(d, field_sys(c), nenv, out, err)) return fail("%s", err.c_str());
+  if (field_validate_desc(d, field_sys(v), nenv, out, err)) return fail("%s", err.c_str());
   aomarl_field *f = new aomarl_field();
   f->nenv = nenv; f->ndir = d->ndir; f->nlayers = d->nlayers; f->inv_lambda = d->inv_lambda;
-  f->W = 2 * c->sys.hw; f->pd = c->sys.pupdiam; f->ref_peak = c->sys.ref_peak;
+  f->W = 2 * v.sys.hw; f->pd = v.sys.pupdiam; f->ref_peak = v.sys.ref_peak;
   f->nblk = (f->pd + FIELD_THREADS / f->W - 1) / (FIELD_THREADS / f->W);
   f->chunk = field_chunk(d->ndir);
   f->off.assign(d->off, d->off + (size_t)2 * d->ndir * d->nlayers);
@@ -356,36 +360,31 @@ int aomarl_field_create(aomarl_ctx *c, int nenv, const aomarl_field_desc *d, aom
   return 0;
 }
 
-// what observe and trace share: the refusals, the waits, the deferred shapes
+// what observe and trace share: the refusals, the waits, the deferred shapes; v: the context's view for the launches
 static int field_prepare(const char *who, aomarl_field *f, aomarl_ctx *c, aomarl_state *st, int b, int n, int flags, int known,
-                         void *stream) {
+                         void *stream, EnvView *v) {
   if (!f || !c || !st) return fail("%s: null argument", who);
-  if (c->pipe.active) return fail("%s: the frame pipeline is on (the frames run a step ahead of the chains)", who);
-  if (c->rp && c->rp->n > 0) return fail("%s: a prefetched reset is in flight", who);
-  if (c->nlayers != f->nlayers || c->sys.pupdiam != f->pd || 2 * c->sys.hw != f->W)
+  int rc = env_refuse_busy(who, c);
+  if (rc) return rc;
+  *v = env_view(c);
+  if (v->nlayers != f->nlayers || v->sys.pupdiam != f->pd || 2 * v->sys.hw != f->W)
     return fail("%s: the field was created on another context (%d layers, pupil %d, window %d)", who, f->nlayers, f->pd, f->W);
   std::string err;
   if (field_validate_call(who, f->nenv, st->nenv, b, n, flags, known, err)) return fail("%s", err.c_str());
-  int rc = check_range(c, st, b, n);
-  if (rc) return rc;
-  rc = atmos_wait_pending(c, stream);
-  if (rc) return rc;
-  if (c->defer_dm_shape && (flags & AOMARL_TRACE_DMS))         // the stack-array shapes exist only as voltages: form them
-    rc = dm_shape_impl(c, st, b, n, nullptr, false, stream);
-  return rc;
+  return env_trace_ready(c, st, b, n, flags, stream);
 }
 
 int aomarl_field_observe(aomarl_field *f, aomarl_ctx *c, aomarl_state *st, int b, int n, int flags, void *stream) {
-  int rc = field_prepare("field_observe", f, c, st, b, n, flags, AOMARL_TRACE_ATMOS | AOMARL_TRACE_DMS, stream);
+  EnvView v;
+  int rc = field_prepare("field_observe", f, c, st, b, n, flags, AOMARL_TRACE_ATMOS | AOMARL_TRACE_DMS, stream, &v);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const DevSys sy = traced_sys(c);
+  const DevSys &sy = v.sys;
   const DevState ds = dev_state(st);
   DevState fst = ds;                                           // the commit's view: the field's record and sum
   fst.strehl = f->record; fst.le_img = f->le;
   for (const FieldLaunch &L : f->plan) {
-    const FieldArgs a = field_args(f->off.data(), f->nlayers, L, c->subpixel_flow ? c->frac_x : nullptr,
-                                   c->subpixel_flow ? c->frac_y : nullptr);
+    const FieldArgs a = field_args(f->off.data(), f->nlayers, L, v.frac_x, v.frac_y);
     const int kt = field_slots(L.count);
     const size_t sm = sizeof(float) * ((size_t)2 * FIELD_THREADS * kt + FIELD_THREADS + (sy.npsf <= FIELD_TW_LDS ? 2 * (size_t)sy.npsf : 0));
 #define FIELD_ROWS(KT)                                                                                                          \
@@ -412,19 +411,19 @@ int aomarl_field_observe(aomarl_field *f, aomarl_ctx *c, aomarl_state *st, int b
 
 int aomarl_field_trace(aomarl_field *f, aomarl_ctx *c, aomarl_state *st, float *planes, int b, int n, int flags, void *stream) {
   if (!planes) return fail("field_trace: null planes");
+  EnvView v;
   int rc = field_prepare("field_trace", f, c, st, b, n, flags,
-                         AOMARL_TRACE_ATMOS | AOMARL_TRACE_DMS | AOMARL_TRACE_RESET | AOMARL_TRACE_MASK, stream);
+                         AOMARL_TRACE_ATMOS | AOMARL_TRACE_DMS | AOMARL_TRACE_RESET | AOMARL_TRACE_MASK, stream, &v);
   if (rc) return rc;
   const int np = f->pd * f->pd;
   for (const FieldLaunch &L : f->plan) {
-    const FieldArgs a = field_args(f->off.data(), f->nlayers, L, c->subpixel_flow ? c->frac_x : nullptr,
-                                   c->subpixel_flow ? c->frac_y : nullptr);
+    const FieldArgs a = field_args(f->off.data(), f->nlayers, L, v.frac_x, v.frac_y);
 #define FIELD_TRACE(KT)                                                                                                          \
-  hipLaunchKernelGGL(k_field_trace<KT>, dim3((np + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, traced_sys(c), dev_state(st), a, \
+  hipLaunchKernelGGL(k_field_trace<KT>, dim3((np + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, v.sys, dev_state(st), a, \
                      L.count, f->ndir, L.first, planes, b, flags)
 #define FIELD_TRACE_ALT(KT)                                                                                                      \
-  hipLaunchKernelGGL(k_field_trace_alt<KT>, dim3((np + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, traced_sys(c),       \
-                     dev_state(st), a, L.count, f->ndir, L.first, planes, b, flags, ma)
+  hipLaunchKernelGGL(k_field_trace_alt<KT>, dim3((np + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, v.sys, dev_state(st), \
+                     a, L.count, f->ndir, L.first, planes, b, flags, ma)
     if (f->mir) {
       const FieldMirArgs ma = field_mir_args(f->mir_base, f->mir_off.data(), L);
       FIELD_DISPATCH(L.count, FIELD_TRACE_ALT);
@@ -449,9 +448,7 @@ int aomarl_field_reset(aomarl_field *f, int b, int n, void *stream) {
   DevState fst;
   memset(&fst, 0, sizeof(fst));
   fst.strehl = f->record; fst.le_img = f->le;
-  hipLaunchKernelGGL(k_strehl_reset, dim3(n * f->ndir), dim3(256), 0, (hipStream_t)stream, sy, fst, b * f->ndir);
-  LAUNCHCHK();
-  return 0;
+  return launch_strehl_reset(sy, fst, b * f->ndir, n * f->ndir, (hipStream_t)stream);
 }
 
 int aomarl_field_get(aomarl_field *f, int do_fit, float **record, float **le, void *stream) {
@@ -464,10 +461,24 @@ int aomarl_field_get(aomarl_field *f, int do_fit, float **record, float **le, vo
     memset(&fst, 0, sizeof(fst));
     fst.strehl = f->record; fst.le_img = f->le;
     // k_strehl_fit_le on the field's buffers: one wave per (environment, direction)
-    hipLaunchKernelGGL(k_strehl_fit_le, dim3(f->nenv * f->ndir), dim3(64), 0, (hipStream_t)stream, sy, fst, 0);
-    LAUNCHCHK();
+    const int rc = launch_strehl_fit_le(sy, fst, 0, f->nenv * f->ndir, (hipStream_t)stream);
+    if (rc) return rc;
   }
   if (record) *record = f->record;
   if (le) *le = f->le;
   return 0;
+}
+
+// ---- for aomarl_field_attach_mirrors / _detach_mirrors (aomarl_mcao.hip; aomarl_env_host.h)
+void field_dims(const aomarl_field *f, int *nenv, int *ndir, int *pupdiam) { *nenv = f->nenv; *ndir = f->ndir; *pupdiam = f->pd; }
+
+void field_set_mirrors(aomarl_field *f, const aomarl_mcao *owner, const FieldMirArgs &base, const float *off) {
+  f->mir_off.assign(off, off + (size_t)2 * f->ndir * base.nmirrors);
+  f->mir_base = base;
+  f->mir = owner;
+}
+
+void field_clear_mirrors(aomarl_field *f) {
+  f->mir = nullptr;
+  f->mir_off.clear();
 }

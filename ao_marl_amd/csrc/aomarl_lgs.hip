@@ -1,8 +1,10 @@
 // aomarl_lgs.hip -- laser guide star on the Shack-Hartmann sensor (include/aomarl.h: aomarl_lgs_*).  gfx950 only.
 // The model is ao_marl_amd/lgs.py (LgsModel, cone_trace_model; float64 NumPy); the reference's host side is
-// shesha/init/lgs_init.py, its native side is not in the reference tree.  Part of aomarl_capi.hip's translation unit:
-// the cone trace reads the context's static description and the state exactly as aomarl_raytrace_wfs does.  The host
-// half is aomarl_lgs_host.h.
+// shesha/init/lgs_init.py, its native side is not in the reference tree.  A translation unit of its own: the cone trace
+// reads the context's static description and the state exactly as aomarl_raytrace_wfs does, through aomarl_env_host.h.
+// The host half is aomarl_lgs_host.h.
+#include "aomarl_env_host.h"
+#include "aomarl_trace_dev.h"
 #include "aomarl_lgs_host.h"
 
 // =============================================================================================
@@ -310,28 +312,23 @@ int aomarl_lgs_set_ref(aomarl_lgs *p, const float *ref) {
 int aomarl_lgs_trace(aomarl_lgs *p, aomarl_ctx *c, aomarl_state *st, const float *dm1, int nlayers, int b, int n, int flags,
                      void *stream) {
   if (!p || !c || !st) return fail("lgs_trace: null argument");
-  if (c->sys.n != p->n) return fail("lgs_trace: the sensor's pupil array is %d wide, the context's %d", p->n, c->sys.n);
+  const EnvView v = env_view(c);
+  if (v.sys.n != p->n) return fail("lgs_trace: the sensor's pupil array is %d wide, the context's %d", p->n, v.sys.n);
   if (st->nenv != p->nenv) return fail("lgs_trace: the sensor has %d environments, the state %d", p->nenv, st->nenv);
-  if (c->pipe.active) return fail("lgs_trace: the frame pipeline is on (the frames run a step ahead of the chains)");
-  if (c->rp && c->rp->n > 0) return fail("lgs_trace: a prefetched reset is in flight");
+  int rc = env_refuse_busy("lgs_trace", c);
+  if (rc) return rc;
   std::string err;
   const int known = AOMARL_TRACE_ATMOS | AOMARL_TRACE_DMS | AOMARL_TRACE_RESET | AOMARL_TRACE_MASK;
-  if (lgs_validate_trace(dm1, nlayers, c->nlayers, AOMARL_MAX_LAYERS, p->nenv, b, n, flags, known, err))
+  if (lgs_validate_trace(dm1, nlayers, v.nlayers, AOMARL_MAX_LAYERS, p->nenv, b, n, flags, known, err))
     return fail("%s", err.c_str());
-  int rc = check_range(c, st, b, n);
-  if (rc) return rc;
-  rc = atmos_wait_pending(c, stream);
+  rc = env_trace_ready(c, st, b, n, flags, stream);
   if (rc) return rc;
   if (!st->wfs_phase) return fail("lgs_trace needs st->wfs_phase");
-  if (c->defer_dm_shape && (flags & AOMARL_TRACE_DMS)) {       // the stack-array shapes exist only as voltages: form them
-    rc = dm_shape_impl(c, st, b, n, nullptr, false, stream);
-    if (rc) return rc;
-  }
   LgsCone cone;
   for (int l = 0; l < AOMARL_MAX_LAYERS; l++) cone.dm1[l] = l < nlayers ? dm1[l] : 0.f;
-  const int np = c->sys.n * c->sys.n;
-  hipLaunchKernelGGL(k_lgs_trace, dim3((np + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, traced_sys(c), dev_state(st),
-                     cone, b, flags);
+  const int np = v.sys.n * v.sys.n;
+  hipLaunchKernelGGL(k_lgs_trace, dim3((np + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, v.sys, dev_state(st), cone, b,
+                     flags);
   LAUNCHCHK();
   return 0;
 }
@@ -365,9 +362,5 @@ int aomarl_lgs_measure(aomarl_lgs *p, const float *phase, int env_begin, int env
   else if (cube) lgs_launch_spot<false, true>(p, pl, phase, env_begin, seeds, frame, image, slopes, s);
   else lgs_launch_spot<false, false>(p, pl, phase, env_begin, seeds, frame, image, slopes, s);
   LAUNCHCHK();
-  if (noisy) {
-    hipLaunchKernelGGL(k_inc_u32, dim3((env_count + 255) / 256), dim3(256), 0, s, frame + env_begin, env_count);
-    LAUNCHCHK();
-  }
-  return 0;
+  return noisy ? launch_inc_u32(frame + env_begin, env_count, s) : 0;
 }

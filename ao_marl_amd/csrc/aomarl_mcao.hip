@@ -1,7 +1,10 @@
 // aomarl_mcao.hip -- multi-conjugate AO: mirrors conjugated to altitude (include/aomarl.h: aomarl_mcao_*).  gfx950 only.
-// The model is ao_marl_amd/mcao.py (mirror_shape_model, mirrors_add_model, delay_line_model; float64 NumPy).  Part of
-// aomarl_capi.hip's translation unit, like aomarl_tomo.hip: the calls read the context's delay, grids and pupils.  The host
-// half is aomarl_mcao_host.h.
+// The model is ao_marl_amd/mcao.py (mirror_shape_model, mirrors_add_model, delay_line_model; float64 NumPy).  A
+// translation unit of its own, like aomarl_tomo.hip: the calls read the context's delay, grids and pupils through
+// aomarl_env_host.h, and hand the science field its mirrors through the same header.  The host half is aomarl_mcao_host.h.
+#include "aomarl_env_host.h"
+#include "aomarl_step_plan_host.h"      // delay_weights
+#include "aomarl_field_host.h"          // FieldMirArgs
 #include "aomarl_mcao_host.h"
 #include "aomarl_mcao_sample.h"
 
@@ -28,10 +31,9 @@ struct aomarl_mcao {
 
 // =============================================================================================
 // k_mcao_apply: the delay line of the altitude mirrors, k_delay's statement on the object's buffers.  It is compiled as
-// k_delay is (the compiler's default contraction): the same expression under the same rules, so that a mirror driven with
-// the simulator's commands carries the simulator's voltages to the bit.
+// k_delay is (the compiler's default contraction, nothing in front of it in this file changes it): the same expression
+// under the same rules, so that a mirror driven with the simulator's commands carries the simulator's voltages to the bit.
 // =============================================================================================
-#pragma clang fp contract(fast)
 __global__ __launch_bounds__(256) void k_mcao_apply(float *__restrict__ com, float *__restrict__ com1, float *__restrict__ com2,
                                                     float *__restrict__ voltage, int nact, float a, float b, float c,
                                                     int env_begin) {
@@ -213,23 +215,16 @@ int aomarl_mcao_com(aomarl_mcao *m, float **com, float **voltage, float **planes
   return 0;
 }
 
-// what apply and add share: the frames that run ahead of the chains
-static int mcao_in_flight(const char *who, const aomarl_ctx *c) {
-  if (c->pipe.active) return fail("%s: the frame pipeline is on (the frames run a step ahead of the chains)", who);
-  if (c->rp && c->rp->n > 0) return fail("%s: a prefetched reset is in flight", who);
-  return 0;
-}
-
 int aomarl_mcao_apply(aomarl_mcao *m, aomarl_ctx *c, int b, int n, const float *volts, void *stream) {
   if (!m || !c) return fail("mcao_apply: null argument");
-  int rc = mcao_in_flight("mcao_apply", c);
+  int rc = env_refuse_busy("mcao_apply", c);
   if (rc) return rc;
   std::string err;
   if (mcao_validate_range("mcao_apply", m->nenv, b, n, err)) return fail("%s", err.c_str());
   hipStream_t s = (hipStream_t)stream;
   const int na = m->dev.nact_total;
   if (!volts) {
-    const DelayWeights dw = delay_weights(c->delay, false);
+    const DelayWeights dw = delay_weights(env_view(c).delay, false);
     hipLaunchKernelGGL(k_mcao_apply, dim3((na + 255) / 256, n), dim3(256), 0, s, m->com, m->com1, m->com2, m->voltage, na, dw.wa,
                        dw.wb, dw.wc, b);
     LAUNCHCHK();
@@ -255,15 +250,16 @@ int aomarl_mcao_reset(aomarl_mcao *m, int b, int n, void *stream) {
 int aomarl_mcao_add(aomarl_mcao *m, aomarl_ctx *c, const aomarl_mcao_view *v, float *planes, int ndir, int nn, int b, int n,
                     int flags, void *stream) {
   if (!m || !c) return fail("mcao_add: null argument");
-  int rc = mcao_in_flight("mcao_add", c);
+  int rc = env_refuse_busy("mcao_add", c);
   if (rc) return rc;
+  const EnvView ev = env_view(c);
   std::string err;
-  if (mcao_validate_add(v, planes, ndir, nn, c->sys.n, c->sys.pupdiam, m->dev.nmirrors, m->dims, m->nenv, b, n, flags,
+  if (mcao_validate_add(v, planes, ndir, nn, ev.sys.n, ev.sys.pupdiam, m->dev.nmirrors, m->dims, m->nenv, b, n, flags,
                         AOMARL_TRACE_MASK, err))
     return fail("%s", err.c_str());
   const McaoAddArgs a = mcao_add_args(v, m->dev.nmirrors);
   // (n == pupdiam: the sensor's grid is the pupil grid's size and its pupil is asked for first, as aomarl_tomo_trace's)
-  const float *pupil = !(flags & AOMARL_TRACE_MASK) ? nullptr : nn == c->sys.n ? c->sys.mpupil : c->sys.spupil;
+  const float *pupil = !(flags & AOMARL_TRACE_MASK) ? nullptr : nn == ev.sys.n ? ev.sys.mpupil : ev.sys.spupil;
   const int np = nn * nn;
 #define MCAO_ADD(KT)                                                                                                          \
   hipLaunchKernelGGL(k_mcao_add<KT>, dim3((np + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, m->dev, a, ndir, m->planes, \
@@ -282,22 +278,23 @@ int aomarl_mcao_add(aomarl_mcao *m, aomarl_ctx *c, const aomarl_mcao_view *v, fl
 // ---- the science field through the mirrors (the field's kernels: aomarl_field.hip, field_pixel<KT, true>)
 int aomarl_field_attach_mirrors(aomarl_field *f, aomarl_mcao *m, const aomarl_mcao_view *v) {
   if (!f || !m) return fail("field_attach_mirrors: null argument");
-  if (f->nenv != m->nenv) return fail("field_attach_mirrors: the field has %d environments, the mirrors %d", f->nenv, m->nenv);
+  int fnenv, fndir, fpd;
+  field_dims(f, &fnenv, &fndir, &fpd);
+  if (fnenv != m->nenv) return fail("field_attach_mirrors: the field has %d environments, the mirrors %d", fnenv, m->nenv);
   std::string err;
-  if (mcao_validate_attach(v, f->ndir, m->dev.nmirrors, m->dims, f->pd, err)) return fail("%s", err.c_str());
-  f->mir_off.assign(v->off, v->off + (size_t)2 * v->ndir * m->dev.nmirrors);
-  memset(&f->mir_base, 0, sizeof(f->mir_base));
-  f->mir_base.planes = m->planes;
-  f->mir_base.nmirrors = m->dev.nmirrors;
-  f->mir_base.stride = m->dev.plane_stride;
-  for (int k = 0; k < m->dev.nmirrors; k++) f->mir_base.dim[k] = m->dims[k];
-  f->mir = m;
+  if (mcao_validate_attach(v, fndir, m->dev.nmirrors, m->dims, fpd, err)) return fail("%s", err.c_str());
+  FieldMirArgs base;
+  memset(&base, 0, sizeof(base));
+  base.planes = m->planes;
+  base.nmirrors = m->dev.nmirrors;
+  base.stride = m->dev.plane_stride;
+  for (int k = 0; k < m->dev.nmirrors; k++) base.dim[k] = m->dims[k];
+  field_set_mirrors(f, m, base, v->off);
   return 0;
 }
 
 int aomarl_field_detach_mirrors(aomarl_field *f) {
   if (!f) return fail("field_detach_mirrors: null object");
-  f->mir = nullptr;
-  f->mir_off.clear();
+  field_clear_mirrors(f);
   return 0;
 }

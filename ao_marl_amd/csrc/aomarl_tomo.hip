@@ -1,7 +1,9 @@
 // aomarl_tomo.hip -- laser tomography (include/aomarl.h: aomarl_tomo_*).  gfx950 only.
-// The model is ao_marl_amd/tomography.py (tomo_trace_model, slope_covariance; float64 NumPy).  Part of aomarl_capi.hip's
-// translation unit, like aomarl_lgs.hip: the trace reads the context's static description and the state.  The host half
-// is aomarl_tomo_host.h.
+// The model is ao_marl_amd/tomography.py (tomo_trace_model, slope_covariance; float64 NumPy).  A translation unit of its
+// own, like aomarl_lgs.hip: the trace reads the context's static description and the state through aomarl_env_host.h.  The
+// host half is aomarl_tomo_host.h.
+#include "aomarl_env_host.h"
+#include "aomarl_trace_dev.h"
 #include "aomarl_tomo_host.h"
 
 // =============================================================================================
@@ -18,37 +20,6 @@ struct TomoArgs {
   float ox[AOMARL_MAX_LAYERS][AOMARL_TOMO_MAX_STARS], oy[AOMARL_MAX_LAYERS][AOMARL_TOMO_MAX_STARS];
   float dm1[AOMARL_MAX_LAYERS][AOMARL_TOMO_MAX_STARS];
 };
-
-// trace_dms<TARGET>'s values one by one: vals[k] is what mirror k adds at pixel (x, y); bit k of the result: it adds
-// (the pixel lies on the mirror).  Expression for expression trace_dms's.  (TARGET: the science field, aomarl_field.hip.)
-template <bool TARGET = false>
-__device__ __forceinline__ unsigned trace_dm_values(const DevSys &sys, const DevState &st, int e, int x, int y,
-                                                    float (&vals)[AOMARL_MAX_DMS]) {
-  unsigned has = 0;
-#pragma unroll
-  for (int k = 0; k < AOMARL_MAX_DMS; k++) {
-    vals[k] = 0.f;
-    if (k < sys.ndm) {
-      const DevDm &D = sys.dms[k];
-      const float fx = (float)x + (TARGET ? D.txo : D.wxo), fy = (float)y + (TARGET ? D.tyo : D.wyo);
-      const int ix = (int)floorf(fx), iy = (int)floorf(fy);
-      if (ix >= 0 && iy >= 0 && ix < D.dim && iy < D.dim) {
-        const float wx = fx - (float)ix, wy = fy - (float)iy;
-        const int ix1 = ix + 1 < D.dim ? ix + 1 : ix, iy1 = iy + 1 < D.dim ? iy + 1 : iy;
-        float v00 = dm_value(sys, st, e, k, ix, iy);
-        if (wx == 0.f && wy == 0.f) {
-          vals[k] = v00;
-        } else {
-          float v01 = dm_value(sys, st, e, k, ix1, iy), v10 = dm_value(sys, st, e, k, ix, iy1);
-          float v11 = dm_value(sys, st, e, k, ix1, iy1);
-          vals[k] = (1.f - wy) * ((1.f - wx) * v00 + wx * v01) + wy * ((1.f - wx) * v10 + wx * v11);
-        }
-        has |= 1u << k;
-      }
-    }
-  }
-  return has;
-}
 
 __global__ __launch_bounds__(256) void k_tomo_trace(DevSys sys, DevState st, TomoArgs a, int K, float *__restrict__ planes,
                                                     int env_begin, int flags) {
@@ -125,34 +96,29 @@ __global__ __launch_bounds__(TOMO_THREADS) void k_tomo_cov(const double *__restr
 int aomarl_tomo_trace(aomarl_ctx *c, aomarl_state *st, const aomarl_tomo_desc *d, float *planes, int b, int n, int flags,
                       void *stream) {
   if (!c || !st) return fail("tomo_trace: null argument");
-  if (c->pipe.active) return fail("tomo_trace: the frame pipeline is on (the frames run a step ahead of the chains)");
-  if (c->rp && c->rp->n > 0) return fail("tomo_trace: a prefetched reset is in flight");
+  int rc = env_refuse_busy("tomo_trace", c);
+  if (rc) return rc;
+  const EnvView v = env_view(c);
   std::string err;
   const int known = AOMARL_TRACE_ATMOS | AOMARL_TRACE_DMS | AOMARL_TRACE_RESET | AOMARL_TRACE_MASK;
   int dims[AOMARL_MAX_LAYERS];
-  for (int l = 0; l < AOMARL_MAX_LAYERS; l++) dims[l] = l < c->nlayers ? c->sys.layers[l].dim : 0;
-  if (tomo_validate_trace(d, planes, c->nlayers, dims, c->sys.n, st->nenv, b, n, flags, known, err))
+  for (int l = 0; l < AOMARL_MAX_LAYERS; l++) dims[l] = l < v.nlayers ? v.sys.layers[l].dim : 0;
+  if (tomo_validate_trace(d, planes, v.nlayers, dims, v.sys.n, st->nenv, b, n, flags, known, err))
     return fail("%s", err.c_str());
-  int rc = check_range(c, st, b, n);
+  rc = env_trace_ready(c, st, b, n, flags, stream);
   if (rc) return rc;
-  rc = atmos_wait_pending(c, stream);
-  if (rc) return rc;
-  if (c->defer_dm_shape && (flags & AOMARL_TRACE_DMS)) {       // the stack-array shapes exist only as voltages: form them
-    rc = dm_shape_impl(c, st, b, n, nullptr, false, stream);
-    if (rc) return rc;
-  }
   TomoArgs a;
   memset(&a, 0, sizeof(a));
   for (int l = 0; l < d->nlayers; l++)
     for (int k = 0; k < d->nstars; k++) {
       const float *o = d->off + 2 * (k * d->nlayers + l);
-      a.ox[l][k] = c->subpixel_flow ? o[0] + c->frac_x[l] : o[0];
-      a.oy[l][k] = c->subpixel_flow ? o[1] + c->frac_y[l] : o[1];
+      a.ox[l][k] = v.frac_x ? o[0] + v.frac_x[l] : o[0];
+      a.oy[l][k] = v.frac_y ? o[1] + v.frac_y[l] : o[1];
       a.dm1[l][k] = d->dm1[k * d->nlayers + l];
     }
-  const int np = c->sys.n * c->sys.n;
-  hipLaunchKernelGGL(k_tomo_trace, dim3((np + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, traced_sys(c), dev_state(st),
-                     a, d->nstars, planes, b, flags);
+  const int np = v.sys.n * v.sys.n;
+  hipLaunchKernelGGL(k_tomo_trace, dim3((np + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, v.sys, dev_state(st), a,
+                     d->nstars, planes, b, flags);
   LAUNCHCHK();
   return 0;
 }
