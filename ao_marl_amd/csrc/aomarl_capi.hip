@@ -1,12 +1,14 @@
 // aomarl_capi.hip -- C ABI (include/aomarl.h) over the gfx950 kernels in aomarl_kernels.hip: context, create / destroy,
 // setters and options here; the entry points by concern in aomarl_capi_atmos / _stages / _agents / _step / _extras /
-// _composites.hip, included at the end (one translation unit: the environment).  Mirror registration, the laser guide
-// star, tomography, the science field and the altitude mirrors are units of their own; what they may ask of a context is
-// defined at the very end (aomarl_env_host.h).
+// _composites.hip, included at the end (one translation unit: the environment).  The one-pass frame kernel is a unit of
+// its own (aomarl_frame.hip, launched through aomarl_frame_host.h).  Mirror registration, the laser guide star, tomography,
+// the science field and the altitude mirrors are units of their own; what they may ask of a context is defined at the
+// very end (aomarl_env_host.h).
 // Host side only sequences kernel launches on the caller's stream; no device<->host copies after
 // aomarl_create / aomarl_set_* (aomarl_reset uploads env_count seeds, 4 bytes each).
 #include "aomarl_kernels.hip"
 #include "aomarl_env_host.h"
+#include "aomarl_frame_host.h"
 #include "aomarl_qf4_host.h"
 #include "aomarl_step_plan_host.h"
 

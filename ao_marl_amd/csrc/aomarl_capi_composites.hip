@@ -86,22 +86,6 @@ static int frame_fused_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, int f
     lds_pad = lds_pad_env >= 0 ? (size_t)lds_pad_env : (smm < two_per_cu ? (two_per_cu - smm + 63) / 64 * 64 : 0);
     if (smm + lds_pad > 64 * 1024) lds_pad = 0;               // (beyond 64 KB the launch would need the opt-in attribute)
   }
-  dim3 grid((n + 3) / 4, c->sys.ntiles), blk(256);
-// the events ride on the dispatch itself (its start / completion signal): no marker packets of their own
-// on the queue in front of and behind the kernel
-#define FW(NL, NB, OTF, NZ, WC, HP) hipExtLaunchKernelGGL((k_frame_wave<NL, NB, OTF, NZ, WC, HP>), grid, blk, smm + lds_pad, s, ev_start, ev_done, 0, c->sys, ds, b, n, cog, TR, TP, w.nblk)
-#define FW_H(NL, NB, OTF, NZ, WC) do { if (hp) FW(NL, NB, OTF, NZ, WC, true); else FW(NL, NB, OTF, NZ, WC, false); } while (0)
-#define FW_NC(NL, NB, OTF)                                                                     \
-  do {                                                                                          \
-    if (noise) { if (cube) FW_H(NL, NB, OTF, true, true); else FW_H(NL, NB, OTF, true, false); }     \
-    else { if (cube) FW_H(NL, NB, OTF, false, true); else FW_H(NL, NB, OTF, false, false); }         \
-  } while (0)
-#define FW_L(NL)                                                          \
-  do {                                                                    \
-    if (!otf) FW_NC(NL, 1, false);                                        \
-    else if (nb == 1) FW_NC(NL, 1, true);                                 \
-    else FW_NC(NL, 2, true);                                              \
-  } while (0)
   const bool timed = !c->capturing && c->time_fw && c->fw_ev_used + 2 <= c->fw_ev.size();
   // closing event: the "readers of the screens are done" mark the side streams wait for (the closing
   // event of a timed launch doubles as it); only with the prefetch on, which is what creates ev_frame
@@ -114,17 +98,14 @@ static int frame_fused_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, int f
   if (timed) { ev_start = c->fw_ev[c->fw_ev_used]; ev_done = c->fw_ev[c->fw_ev_used + 1]; c->fw_ev_used += 2; }
   hipEvent_t ev_mark = nullptr;
   if (c->capturing) { ev_mark = ev_done; ev_start = nullptr; ev_done = nullptr; }   // a captured dispatch carries no events
-  if (c->nlayers == 1) FW_L(1); else FW_L(3);
+  const FrameLaunch fl = {c->nlayers == 1 ? 1 : 3, nb, otf, noise, cube, hp,
+                          dim3((n + 3) / 4, c->sys.ntiles), smm + lds_pad, s, ev_start, ev_done,
+                          &c->sys, ds, b, n, cog, TR, TP, w.nblk};
+  rc = launch_frame_wave(fl, c->fw_variant);   // (aomarl_frame.hip; fw_variant: what it launched, aomarl_frame_kernel_name)
+  if (rc) return rc;
   if (ev_mark) { HIPCHK(hipEventRecord(ev_mark, s)); ev_done = ev_mark; }
   c->frame_marked = false;
-  c->fw_variant[0] = c->nlayers == 1 ? 1 : 3; c->fw_variant[1] = otf ? nb : 1; c->fw_variant[2] = otf;
-  c->fw_variant[3] = noise; c->fw_variant[4] = cube; c->fw_variant[5] = hp;
   g_arith[hp ? AR_FRAME_SPLIT : AR_FRAME_F32]++;
-#undef FW_L
-#undef FW_NC
-#undef FW_H
-#undef FW
-  LAUNCHCHK();
   if (slot >= 0) {
     c->pipe.ev_done_cur[slot] = ev_done;
     HIPCHK(hipStreamWaitEvent(c->psf_stream, ev_done, 0));
@@ -335,6 +316,11 @@ int gemm_batched_launch(int batch, int transA, int transB, int M, int N, int K, 
 #undef GG
 }
 
+bool gemm_p_launch_cfg(const GemmPCfg &c, int M, int N, int K, float alpha, const float *A, int lda, const float *B,
+                       int ldb, float beta, float *C, int ldc, float *P, int xcd, hipStream_t s) {
+  return gemm_p_launch(c, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, P, xcd, s);
+}
+
 // Every batched product of the C ABI: the grouped kernel of the learner (aomarl_gemm_g.h: operands in either
 // orientation, bias / ReLU epilogue) when every operand row starts on 16 bytes, round 1's general kernel otherwise
 // (odd leading dimensions, accumulation into C).  transA: A is [K][M]; transB: B is [K][N] (else [N][K]).
@@ -351,7 +337,7 @@ static int gemm_batched_any(int batch, int transA, int transB, int M, int N, int
   const bool whole = !((transA ? M : K) & 3) && !((transB ? N : K) & 3);
   if (al && whole && !accumulate && K > 0 && !g_gemm_kgroups) {
     return gemm_g_batched(batch, !transA, !transB, M, N, K, A, lda, strideA, B, ldb, strideB, bias, strideBias, C, ldc,
-                          strideC, relu, s);
+                          strideC, relu, nullptr, 0, s);
   }
   return gemm_batched_launch(batch, transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB, bias, strideBias, C, ldc,
                              strideC, relu, accumulate, nullptr, 0, 0, s);

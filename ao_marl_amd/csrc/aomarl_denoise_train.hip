@@ -9,7 +9,8 @@
 //   convT4x4s2(64->32)+ReLU -> convT4x4s2(32->16)+ReLU -> convT3x3s1(16->1)
 //
 // Every product -- forward, input gradient, weight gradient -- is one launch of the learner's grouped GEMM
-// (aomarl_gemm_g.h, v_mfma_f32_16x16x4_f32), with gather / fold kernels around it:
+// (aomarl_gemm_g.h, v_mfma_f32_16x16x4_f32; launched through gemm_g_batched of aomarl_sac.hip, the one unit that
+// instantiates it), with gather / fold kernels around it:
 //  * activations are channel-last [image][y][x][C], so they ARE row-major GEMM operands;
 //  * a convolution is  col = gather(in) [positions][Cin 9],  Z = col W^T + b  with W as the checkpoint holds it
 //    ([Cout][Cin 9], k contiguous); its weight gradient is col^T dZ, its input gradient fold(dZ W);
@@ -28,7 +29,6 @@
 // Adam keeps its two moments in double and rounds the new weight once: the update is torch.optim.Adam's formula
 // evaluated on the fp32 gradients to the last bit of the fp32 weight.
 #include "aomarl_host.h"
-#include "aomarl_gemm_g.h"
 #include <vector>
 #include <math.h>
 #include <string.h>
@@ -317,15 +317,8 @@ int aomarl_denoiser_trainer_create(const float *const *wt, const float *const *b
 static int dt_gemm(int groups, bool ak, bool bk, int M, int N, int K, const float *A, int lda, long long sA,
                    const float *B, int ldb, long long sB, float *C, int ldc, long long sC, const float *bias, int relu,
                    const float *mask, int ldm, hipStream_t s) {
-  GemmGArgs a;
-  memset(&a, 0, sizeof(a));
-  a.M = M; a.N = N; a.K = K;
-  a.A = A; a.lda = lda; a.sA = sA;
-  a.B = B; a.ldb = ldb; a.sB = sB;
-  a.C = C; a.ldc = ldc; a.sC = sC;
-  a.bias = bias; a.relu = relu;
-  a.mask = mask; a.ldm = ldm;
-  if (gemm_g_launch(groups, ak, bk, a, 0, 0, s)) return fail("denoiser_trainer: GEMM launch failed (%d x %d x %d)", M, N, K);
+  if (gemm_g_batched(groups, ak, bk, M, N, K, A, lda, sA, B, ldb, sB, bias, 0, C, ldc, sC, relu, mask, ldm, s))
+    return fail("denoiser_trainer: GEMM launch failed (%d x %d x %d)", M, N, K);
   g_arith[AR_GEMM_F32]++;
   return 0;
 }

@@ -326,7 +326,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_g(const GemmGArgs a) {
 // gradient; the policy's first layer and the critics' hidden layer on the gathered batch) share a grid instead of
 // meeting through events on two streams (an event record or wait on the critical stream cost 6 - 7.5 us each,
 // profiles/r05a_sac_update_timeline.txt).  A workgroup belongs to one problem: the form switch is block-uniform.
-// (static: this header is included by more than one translation unit of the library.)
+// (static: a program may include this header in more than one translation unit.)
 #define GG_MAXP 3
 struct GemmGMulti {
   int np;

@@ -1,5 +1,5 @@
 // aomarl_gemm_nt.h -- the 64 x 64 GEMM kernels of the environment unit (included by aomarl_kernels.hip, after the
-// split-fp16 helpers): k_gemm_nt, k_gemm_nt_h, k_gemm_batched_gen, the split-K reduces, and launch_gemm_nt, the one
+// split-fp16 helpers of aomarl_spot_dev.h): k_gemm_nt, k_gemm_nt_h, k_gemm_batched_gen, the split-K reduces, and launch_gemm_nt, the one
 // host function every product of the AO loop goes through (its decisions: aomarl_gemm_plan_host.h).
 #pragma once
 #include "aomarl_gemm_plan_host.h"

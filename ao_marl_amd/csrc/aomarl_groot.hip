@@ -8,9 +8,10 @@
 //                    the workgroup's batch entry are staged in LDS; the Ij0 table (160 KB) is read through L2: a wave's
 //                    64 separations fall into a handful of neighbouring table intervals.
 //   k_groot_reduce   the fixed-order sum of a product's k-split slabs
-// The sandwich G C G^T runs on k_gemm_p (aomarl_gemm_p.h), twice: T = G C^T, out = G T^T.
+// The sandwich G C G^T runs on k_gemm_p (aomarl_gemm_p.h, through the environment unit's gemm_p_launch_cfg), twice:
+// T = G C^T, out = G T^T.
 #include "aomarl_host.h"
-#include "aomarl_gemm_p.h"
+#include "aomarl_gemm_p_host.h"   // GemmPCfg, gemm_p_pick
 #include "aomarl_groot_host.h"
 #include <string.h>
 
@@ -128,7 +129,7 @@ static int gr_product(aomarl_groot *g, int M, int N, int K, const float *A, int 
                       int ldc, int add, hipStream_t s) {
   const GemmPCfg c = gemm_p_pick(M, N, K, g->ws_floats, GR_MAX_SPLIT);
   if (c.wm == 0) return fail("groot_sandwich: no configuration of the matrix kernel for %d x %d x %d", M, N, K);
-  if (!gemm_p_launch(c, M, N, K, 1.f, A, lda, B, ldb, add ? 1.f : 0.f, C, ldc, g->ws, 1, s))
+  if (!gemm_p_launch_cfg(c, M, N, K, 1.f, A, lda, B, ldb, add ? 1.f : 0.f, C, ldc, g->ws, 1, s))
     return fail("groot_sandwich: the matrix kernel could not be launched (tile %d x %d)", c.wm, c.wn);
   LAUNCHCHK();
   g_arith[AR_GEMM_F32]++;

@@ -1,7 +1,7 @@
 // aomarl_host.h -- host-side pieces shared by the translation units of libaomarl_hip.so (aomarl_capi.hip: context,
 // frame / atmosphere / control kernels and their entry points; aomarl_capi_dmreg.hip, aomarl_lgs.hip, aomarl_tomo.hip,
 // aomarl_field.hip, aomarl_mcao.hip: what traces on a context, through aomarl_env_host.h; aomarl_denoise.hip: the denoiser;
-// aomarl_denoise_train.hip: its training step (includes aomarl_gemm_g.h itself); aomarl_sac.hip: the learner's update and the grouped GEMM; aomarl_roket.hip: the ROKET filter bank; aomarl_psfrec.hip: the PSF reconstruction; aomarl_groot.hip: the GROOT covariance model; aomarl_modopti.hip: the modal-gain filter bank; aomarl_predictor.hip: the modal predictor).  Not part of the C ABI: hidden visibility.
+// aomarl_denoise_train.hip: its training step; aomarl_sac.hip: the learner's update and the grouped GEMM; aomarl_roket.hip: the ROKET filter bank; aomarl_psfrec.hip: the PSF reconstruction; aomarl_groot.hip: the GROOT covariance model; aomarl_modopti.hip: the modal-gain filter bank; aomarl_predictor.hip: the modal predictor).  Not part of the C ABI: hidden visibility.
 #pragma once
 #include "aomarl_dev.h"
 
@@ -34,11 +34,17 @@ AOMARL_LOCAL int gemm_batched_launch(int batch, int transA, int transB, int M, i
                                      const float *bias, long long strideBias, float *C, int ldc, long long strideC,
                                      int relu, int accumulate, const float *mask, int ldm, long long strideM,
                                      hipStream_t s);
-// one launch of the grouped kernel (aomarl_gemm_g.h, instantiated in aomarl_sac.hip): C[g] = act(opA(A[g]) opB(B[g]) + bias[g]);
-// ak / bk: the operand is contiguous along k
+// one launch of the grouped kernel (aomarl_gemm_g.h, instantiated in aomarl_sac.hip alone): C[g] = act(opA(A[g]) opB(B[g]) +
+// bias[g]), zero where mask[m][n] <= 0 (rows ldm apart, one mask for every group; null: none); ak / bk: the operand is
+// contiguous along k
 AOMARL_LOCAL int gemm_g_batched(int batch, bool ak, bool bk, int M, int N, int K, const float *A, int lda, long long sA,
                                 const float *B, int ldb, long long sB, const float *bias, long long sBias, float *C, int ldc,
-                                long long sC, int relu, hipStream_t s);
+                                long long sC, int relu, const float *mask, int ldm, hipStream_t s);
+// gemm_p_launch out of line: one launch of k_gemm_p (aomarl_gemm_p.h, instantiated in the environment's unit alone) with
+// a configuration of gemm_p_pick (aomarl_gemm_p_host.h); false: not launched
+struct GemmPCfg;
+AOMARL_LOCAL bool gemm_p_launch_cfg(const GemmPCfg &c, int M, int N, int K, float alpha, const float *A, int lda,
+                                    const float *B, int ldb, float beta, float *C, int ldc, float *P, int xcd, hipStream_t s);
 
 // the on-line modal-gain optimiser (aomarl_modopti.hip) as aomarl_do_control sees it while one is attached
 // (aomarl_modopti_online_attach, aomarl_capi_stages.hip): p = v2m . voltage goes into mo_online_p, mo_online_pol writes

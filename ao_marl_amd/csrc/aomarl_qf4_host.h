@@ -1,4 +1,4 @@
-// The per-lane constants of the slopes-only frame kernel's four-product moments (aomarl_kernels.hip:
+// The per-lane constants of the slopes-only frame kernel's four-product moments (aomarl_spot_dev.h:
 // spot_qf_moments), built on the host in double precision.  Plain C++, no HIP, no library: the same table on
 // every host (fixed sweep orders, fixed tie-breaks; the only library calls are sin, cos, sqrt).
 //

@@ -632,14 +632,15 @@ int aomarl_sac_update(aomarl_sac *s, const float *state, const float *next_state
 }
 
 // ---------------------------------------------------------------- the grouped kernel for the C ABI's batched products
+// (and, with the mask epilogue, for the denoiser's training step: this unit alone instantiates k_gemm_g)
 int gemm_g_batched(int batch, bool ak, bool bk, int M, int N, int K, const float *A, int lda, long long sA,
                    const float *B, int ldb, long long sB, const float *bias, long long sBias, float *C, int ldc,
-                   long long sC, int relu, hipStream_t s) {
+                   long long sC, int relu, const float *mask, int ldm, hipStream_t s) {
   GemmGArgs g;
   memset(&g, 0, sizeof(g));
   g.M = M; g.N = N; g.K = K;
   g.A = A; g.lda = lda; g.sA = sA; g.B = B; g.ldb = ldb; g.sB = sB; g.C = C; g.ldc = ldc; g.sC = sC;
-  g.bias = bias; g.sBias = sBias; g.relu = relu;
+  g.bias = bias; g.sBias = sBias; g.relu = relu; g.mask = mask; g.ldm = ldm;
   if (gemm_g_launch(batch, ak, bk, g, 0, 0, s)) return fail("gemm_batched: k_gemm_g launch failed");
   return 0;
 }

@@ -1,4 +1,4 @@
-"""The slopes-only fp32 frame kernel (moments from four matrix products, csrc/aomarl_kernels.hip: spot_qf_moments)
+"""The slopes-only fp32 frame kernel (moments from four matrix products, csrc/aomarl_spot_dev.h: spot_qf_moments)
 against the float64 centre of gravity of the phase it receives (tests/phase_range.py: slopes64), on screens that pin
 what the folded constants of its table decide: (i) a pure x tilt, (ii) a pure y tilt of another size and the other
 sign -- axis and sign of both slopes -- and (iii) random tilts of up to +-6 revolutions per sub-aperture with a little

@@ -1,4 +1,4 @@
-"""The identity the slopes-only frame kernel rests on (csrc/aomarl_kernels.hip: spot_cog_qf): the centre of gravity of
+"""The identity the slopes-only frame kernel rests on (csrc/aomarl_spot_dev.h: spot_cog_qf): the centre of gravity of
 a noise-free, fully binned Shack-Hartmann spot is a ratio of quadratic forms of the pupil field, so the spot itself
 never has to be formed.  Checked here on the CPU against the definition the oracle restates (zero-padded FFT of the
 half-pixel-shifted field, |.|^2, binmap, moments: geom_init.py:689-758, wfsCompass.py:334-343) with the reference's own

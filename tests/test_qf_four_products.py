@@ -1,5 +1,5 @@
 """The slopes-only frame kernel takes the three moments of a sub-aperture from FOUR matrix products
-(csrc/aomarl_kernels.hip: spot_qf_moments): both Toeplitz kernels factor through one real basis,
+(csrc/aomarl_spot_dev.h: spot_qf_moments): both Toeplitz kernels factor through one real basis,
 
     M = H' H'^T,      S = H' L H'^T,      L = 2 x 2 blocks [[0, t_k], [-t_k, 0]],
 

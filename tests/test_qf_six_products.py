@@ -1,5 +1,5 @@
 """The slopes-only frame kernel takes the three moments of a sub-aperture from SIX matrix products
-(csrc/aomarl_kernels.hip: spot_qf_moments): with Wr = M Er^T, Wi = M Ei^T the one accumulator
+(csrc/aomarl_spot_dev.h: spot_qf_moments): with Wr = M Er^T, Wi = M Ei^T the one accumulator
 
     X = (Er + Ei) Wr + (Ei - Er) Wi = G1 + (G2 - G2^T),    G1 = Er Wr + Ei Wi (symmetric),  G2 = Ei Wr
 

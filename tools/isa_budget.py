@@ -5,7 +5,7 @@ waits and s_nops -- the static side of the counters in profiles/r*_pmc_frame_ker
 
     python tools/isa_budget.py [--kernel REGEX] [--asm FILE] [--lines]
 
-Without --asm the environment's translation unit is compiled to assembly first (hipcc --cuda-device-only -S, ~40 s).
+Without --asm the frame kernel's translation unit is compiled to assembly first (hipcc --cuda-device-only -S, ~30 s).
 Default kernel: the bench's frame-kernel instantiation k_frame_wave<3, 1, true, false, false, false>.
 profiles/r06_frame_kernel_isa_budget.txt is this output, annotated by hand with the source construct of every block."""
 import argparse
@@ -58,10 +58,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernel", default=r"_Z12k_frame_waveILi3ELi1ELb1ELb0ELb0ELb0EE")
     ap.add_argument("--asm", default=None)
-    ap.add_argument("--source", default="aomarl_capi.hip",
-                    help="translation unit under ao_marl_amd/csrc (default: the environment, which holds the frame kernel; "
-                         "aomarl_capi_dmreg.hip, aomarl_lgs.hip, aomarl_tomo.hip, aomarl_field.hip and aomarl_mcao.hip are units "
-                         "of their own, like the denoiser, the learner and the rest of csrc/Makefile's UNITS)")
+    ap.add_argument("--source", default="aomarl_frame.hip",
+                    help="translation unit under ao_marl_amd/csrc (default: the frame kernel's; aomarl_capi.hip is the rest of "
+                         "the environment; aomarl_capi_dmreg.hip, aomarl_lgs.hip, aomarl_tomo.hip, aomarl_field.hip and "
+                         "aomarl_mcao.hip are units of their own, like the denoiser, the learner and the rest of csrc/Makefile's "
+                         "UNITS)")
     ap.add_argument("--lines", action="store_true", help="print every instruction with its category")
     a = ap.parse_args()
     asm = a.asm

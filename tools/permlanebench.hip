@@ -1,6 +1,6 @@
 // Development aid (round 6): what v_permlane32_swap_b32 / v_permlane16_swap_b32 (new on gfx950) do to a wave, lane by
 // lane, and what they cost beside the DPP adds of the frame kernel's reductions -- the three moments of a sub-aperture
-// summed over the wave in 10 instructions instead of 3 x 7 (spot_cog_qf, ao_marl_amd/csrc/aomarl_kernels.hip).
+// summed over the wave in 10 instructions instead of 3 x 7 (spot_cog_qf, ao_marl_amd/csrc/aomarl_spot_dev.h).
 //   hipcc --offload-arch=gfx950 -O2 -o tools/bin/permlanebench tools/permlanebench.hip && tools/bin/permlanebench
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -1,5 +1,5 @@
 """The centre of gravity of a noise-free Shack-Hartmann spot as a quadratic form of the pupil field
-(csrc/aomarl_kernels.hip: spot_cog_qf) against the definition: zero-padded 64 x 64 FFT of the half-pixel-shifted
+(csrc/aomarl_spot_dev.h: spot_cog_qf) against the definition: zero-padded 64 x 64 FFT of the half-pixel-shifted
 field, |.|^2, binmap, moments (geom_init.py:689-758, the oracle's aoref_sh_image + aoref_cog), in float64 and
 with the products rounded to float32.  CPU only:  python tools/qf_cog_check.py
 """
@@ -85,7 +85,7 @@ def four_product_basis(N=64, nf=16):
 def cog_four_products(H, t, phase_rev, amp, dt, field=None):
     """The same moments from FOUR products (the kernel's form): with P = H'^T E H' (E H' for the real and the imaginary
     part, then H'^T . of each)  sum I = |P|^2 and the first moments pair neighbouring columns / rows of P_r, P_i with
-    t_k (csrc/aomarl_kernels.hip: spot_qf_moments).  `H`, `t` as four_product_basis returns them."""
+    t_k (csrc/aomarl_spot_dev.h: spot_qf_moments).  `H`, `t` as four_product_basis returns them."""
     if field is None:
         E = amp * np.exp(2j * np.pi * phase_rev)
         field = E.real, E.imag
