@@ -9,7 +9,7 @@
 #include "aomarl_kernels.hip"
 #include "aomarl_env_host.h"
 #include "aomarl_frame_host.h"
-#include "aomarl_qf4_host.h"
+#include "aomarl_create_plan_host.h"
 #include "aomarl_step_plan_host.h"
 
 #include <math.h>
@@ -44,7 +44,7 @@ struct aomarl_ctx {
   int nclass = 0;
   int maxdim = 0, maxK = 0;
   float gain = 0.f, delay = 0.f;
-  bool spot_fast = false;
+  bool production_layout = false;     // two mirrors, a stack array then a tip-tilt, one or three layers (CreatePlan)
   bool force_generic_dm = false, force_valu_target = false;
   bool force_generic_spot = false, force_generic_target = false, force_unfused_frame = false;
   int dft_mode = -1;                   // frame kernel DFTs: -1 follow the library's precision mode, 0 fp32 MFMAs, 1 split-fp16 ("force_f32_dft")
@@ -244,449 +244,52 @@ static int upload(aomarl_ctx *c, const T *host, size_t n, T **dev) {
   return 0;
 }
 
-static bool is_int(float v) { return floorf(v) == v; }
-
+// Creation: the plan decides everything on the host (aomarl_create_plan_host.h: the refusals, the DevSys, the tables),
+// then each table is one allocation, one copy and one pointer store.  All validation precedes the first HIP call.
 int aomarl_create(const aomarl_desc *d, aomarl_ctx **out) {
   if (!d || !out) return fail("aomarl_create: null argument");
-  if (d->abi_version != AOMARL_ABI_VERSION)
-    return fail("aomarl_create: ABI version %d, library is %d", d->abi_version, AOMARL_ABI_VERSION);
-  if (d->nlayers < 0 || d->nlayers > AOMARL_MAX_LAYERS) return fail("nlayers out of range");
-  if (d->ndm < 1 || d->ndm > AOMARL_MAX_DMS) return fail("ndm out of range");
-  if (d->n <= 0 || d->pupdiam <= 0 || d->n < d->pupdiam) return fail("bad pupil sizes");
-  if (d->pupdiam % 4 || d->n % 4) return fail("pupil grid sizes must be multiples of 4");
-  if (d->npsf & (d->npsf - 1)) return fail("npsf must be a power of two");
-  if (!(d->strehl_halfwin == 4 || d->strehl_halfwin == 8 || d->strehl_halfwin == 16))
-    return fail("strehl_halfwin must be 4, 8 or 16");
+  CreatePlan P;
+  if (!create_plan(d, P)) return fail("%s", P.msg);
   aomarl_ctx *c = new aomarl_ctx();
-  DevSys &s = c->sys;
-  memset(&s, 0, sizeof(s));
+  const CreateHost &H = P.host;
+  c->sys = P.sys;
+  c->nlayers = P.sys.nlayers; c->ndm = P.sys.ndm;
+  for (int l = 0; l < c->nlayers; l++) {
+    c->dim[l] = H.dim[l]; c->ns[l] = H.ns[l]; c->abclass[l] = H.abclass[l];
+    c->deltax[l] = H.deltax[l]; c->deltay[l] = H.deltay[l];
+  }
+  c->nclass = H.nclass; c->maxdim = H.maxdim; c->maxK = H.maxK; c->small_ok = H.small_ok;
+  c->gain = H.gain; c->delay = H.delay;
+  c->h_grid = H.h_grid; c->h_prof = H.h_prof; c->h_spupil = H.h_spupil; c->h_tt = H.h_tt;
+  c->production_layout = P.production_layout;
   int rc = 0;
-#define UP(T, host, n, dev)                                      \
-  do {                                                           \
-    T *_p;                                                       \
-    rc = upload<T>(c, host, n, &_p);                             \
-    if (rc) { aomarl_destroy(c); return rc; }                    \
-    dev = _p;                                                    \
-  } while (0)
-  s.n = d->n; s.pupdiam = d->pupdiam;
-  UP(float, d->mpupil, (size_t)d->n * d->n, s.mpupil);
-  UP(float, d->spupil, (size_t)d->pupdiam * d->pupdiam, s.spupil);
-  c->h_spupil.assign(d->spupil, d->spupil + (size_t)d->pupdiam * d->pupdiam);
-  s.nvalid = d->nvalid; s.pdiam = d->pdiam; s.nfft = d->nfft; s.npix = d->npix;
-  s.nrebin = d->nrebin; s.nxsub = d->nxsub;
-  const int pd2 = d->pdiam * d->pdiam;
-  UP(int32_t, d->phasemap, (size_t)pd2 * d->nvalid, s.phasemap);
-  // every sub-aperture must be a contiguous pdiam x pdiam tile of the phase grid
-  std::vector<int32_t> sub(d->nvalid);
-  for (int i = 0; i < d->nvalid; i++) {
-    int p0 = d->phasemap[i];
-    int x0 = p0 % d->n, y0 = p0 / d->n;
-    if (x0 + d->pdiam > d->n || y0 + d->pdiam > d->n) { aomarl_destroy(c); return fail("phasemap tile outside the phase grid"); }
-    for (int k = 0; k < pd2; k++)
-      if (d->phasemap[(size_t)k * d->nvalid + i] != p0 + (k % d->pdiam) + d->n * (k / d->pdiam)) {
-        aomarl_destroy(c);
-        return fail("phasemap of sub-aperture %d is not a contiguous tile", i);
-      }
-    sub[i] = x0 | (y0 << 16);
+  for (size_t i = 0; i < P.tables.size() && !rc; i++) {
+    const CreateTable &T = P.tables[i];
+    unsigned char *p = nullptr;
+    rc = upload<unsigned char>(c, (const unsigned char *)T.data(), T.bytes, &p);
+    for (size_t off : T.slots) memcpy((char *)&c->sys + off, &p, sizeof(p));
   }
-  UP(int32_t, sub.data(), sub.size(), s.sub_xy);
-  std::vector<float> hrev(pd2);
-  for (int k = 0; k < pd2; k++) hrev[k] = (float)((double)d->halfxy[k] / (2.0 * M_PI));
-  UP(float, hrev.data(), hrev.size(), s.halfxy);
-  UP(int32_t, d->binmap, (size_t)d->nrebin * d->nrebin * d->npix * d->npix, s.binmap);
-  UP(float, d->flux, (size_t)d->nvalid, s.flux);
-  UP(int32_t, d->validsubsx, (size_t)d->nvalid, s.validx);
-  UP(int32_t, d->validsubsy, (size_t)d->nvalid, s.validy);
-  s.nphot = d->nphot; s.wfs_inv_lambda = 1.0f / d->wfs_lambda; s.noise = d->noise;
-  s.cog_offset = d->cog_offset; s.cog_scale = d->cog_scale; s.subapd = d->subapd;
-  c->spot_fast = (d->pdiam == 16 && d->nfft == 64 && d->nrebin == 2 && d->npix == 16);
-  if (c->spot_fast) {
-    // the kernel hard-codes the binmap of this sampling: LR (Y, X) <- HR rows/cols
-    // (2Y-16 .. 2Y-15) mod 64 ; check the map handed in says the same
-    for (int px = 0; px < 256 && c->spot_fast; px++) {
-      int Y = px / 16, X = px % 16;
-      bool seen[4] = {false, false, false, false};
-      for (int r = 0; r < 4; r++) {
-        int hr = d->binmap[r * 256 + px];
-        int ky = hr / 64, kx = hr % 64;
-        int dy = (ky - (2 * Y - 16) + 64) % 64, dx = (kx - (2 * X - 16) + 64) % 64;
-        if (dy > 1 || dx > 1) { c->spot_fast = false; break; }
-        seen[dy * 2 + dx] = true;
+  if (!rc && P.psf_operand >= 0) {
+    // the [hi | lo] split-fp16 form of the frame kernel's PSF operand: per lane 4 floats -> [hi(j = 0..3) | lo(j = 0..3)]
+    const CreateTable &T = P.tables[P.psf_operand];
+    const float *twf = (const float *)T.data();
+    std::vector<_Float16> tw(T.bytes / sizeof(float) * 2);
+    for (size_t q = 0; q < T.bytes / sizeof(float) / 4; q++)
+      for (int j = 0; j < 4; j++) {
+        const float v = twf[q * 4 + j];
+        const _Float16 hi = (_Float16)v;
+        const _Float16 lo = (_Float16)(v - (float)hi);
+        tw[q * 8 + j] = hi; tw[q * 8 + 4 + j] = lo;
       }
-      if (!(seen[0] && seen[1] && seen[2] && seen[3])) c->spot_fast = false;
-    }
+    _Float16 *dev = nullptr;
+    rc = upload<_Float16>(c, tw.data(), tw.size(), &dev);
+    c->sys.psf_tw_h = dev;
   }
-  if (c->spot_fast) {
-    // the kernel folds the half-pixel ramp into half-integer DFT frequencies: it must be the
-    // reference's halfxy = pi (x + y) / Nfft (geom_init.py:689-692)
-    for (int k = 0; k < pd2 && c->spot_fast; k++) {
-      double want = M_PI * (double)((k % d->pdiam) + (k / d->pdiam)) / (double)d->nfft;
-      if (fabs((double)d->halfxy[k] - want) > 2e-6) c->spot_fast = false;
-    }
+  if (rc) { aomarl_destroy(c); return rc; }
+  for (int cls = 0; cls < H.nclass; cls++) {
+    const CreateTable &T = P.tables[P.ab_table[cls]];
+    c->ab_scale[cls] = gemm_scale((const float *)T.data(), T.bytes / sizeof(float));
   }
-  if (!c->spot_fast) {
-    aomarl_destroy(c);
-    return fail("unsupported WFS sampling (pdiam=%d nfft=%d nrebin=%d npix=%d, binmap, halfxy): the "
-                "spot kernel is specialised for 16/64/2/16 with the standard half-pixel ramp",
-                d->pdiam, d->nfft, d->nrebin, d->npix);
-  }
-  // layers
-  c->nlayers = s.nlayers = d->nlayers;
-  long long off = 0;
-  const float *seenA[AOMARL_MAX_LAYERS]; const float *seenB[AOMARL_MAX_LAYERS];
-  const float *devAB[AOMARL_MAX_LAYERS]; int ldab[AOMARL_MAX_LAYERS];
-  const float *devABt[AOMARL_MAX_LAYERS]; int ldt[AOMARL_MAX_LAYERS];
-  c->small_ok = true;
-  s.wfs_all_int = 1; s.tar_all_int = 1;
-  for (int l = 0; l < d->nlayers; l++) {
-    const aomarl_layer_desc &L = d->layers[l];
-    DevLayer &D = s.layers[l];
-    if (L.dim <= 0 || L.dim > 65535 || L.nstencil <= 0) { aomarl_destroy(c); return fail("bad layer %d", l); }
-    // the mirror columns repeat the row's first RING_PAD pixels: a narrower screen would mirror pixels it is
-    // writing (k_refresh_mirror, k_set_screen, the scatter's px < RING_PAD)
-    if (L.dim < RING_PAD) { aomarl_destroy(c); return fail("layer %d: a screen of %d pixels is narrower than the ring's %d mirror columns", l, L.dim, RING_PAD); }
-    D.dim = L.dim; D.ns = L.nstencil; D.screen_off = off; off += (long long)L.dim * (L.dim + RING_PAD);
-    c->dim[l] = L.dim; c->ns[l] = L.nstencil; c->deltax[l] = L.deltax; c->deltay[l] = L.deltay;
-    if (L.dim > c->maxdim) c->maxdim = L.dim;
-    if (L.dim + L.nstencil > c->maxK) c->maxK = L.dim + L.nstencil;
-    std::vector<uint32_t> ix(L.nstencil), iy(L.nstencil);
-    for (int k = 0; k < L.nstencil; k++) {
-      if (L.istx[k] >= (uint32_t)(L.dim * L.dim) || L.isty[k] >= (uint32_t)(L.dim * L.dim)) { aomarl_destroy(c); return fail("stencil index out of range"); }
-      ix[k] = (L.istx[k] % L.dim) | ((L.istx[k] / L.dim) << 16);
-      iy[k] = (L.isty[k] % L.dim) | ((L.isty[k] / L.dim) << 16);
-    }
-    UP(uint32_t, ix.data(), ix.size(), D.istx);
-    UP(uint32_t, iy.data(), iy.size(), D.isty);
-    {
-      std::vector<uint32_t> it(ix.size());
-      for (size_t k = 0; k < ix.size(); k++) it[k] = (ix[k] >> 16) | (ix[k] << 16);
-      UP(uint32_t, it.data(), it.size(), D.istT);
-    }
-    // [A | B] concatenated, shared between layers that were given the same host matrices
-    int cls = -1;
-    for (int m = 0; m < c->nclass; m++)
-      if (seenA[m] == L.A && seenB[m] == L.B) cls = m;
-    if (cls < 0) {
-      cls = c->nclass++;
-      seenA[cls] = L.A; seenB[cls] = L.B;
-      int K = L.nstencil + L.dim;
-      int ld = (K + 3) & ~3;
-      std::vector<float> ab((size_t)L.dim * ld, 0.f);
-      for (int r = 0; r < L.dim; r++) {
-        memcpy(&ab[(size_t)r * ld], L.A + (size_t)r * L.nstencil, sizeof(float) * L.nstencil);
-        memcpy(&ab[(size_t)r * ld + L.nstencil], L.B + (size_t)r * L.dim, sizeof(float) * L.dim);
-      }
-      float *p;
-      UP(float, ab.data(), ab.size(), p);
-      devAB[cls] = p; ldab[cls] = ld;
-      devABt[cls] = nullptr; ldt[cls] = 0;
-      if (L.dim <= MOVE_SMALL_DIM && K <= MOVE_SMALL_K) {          // small screens: the transpose for k_move_small
-        const int lt = (L.dim + 63) & ~63;
-        std::vector<float> abt((size_t)K * lt, 0.f);
-        for (int r = 0; r < L.dim; r++)
-          for (int j = 0; j < K; j++) abt[(size_t)j * lt + r] = ab[(size_t)r * ld + j];
-        float *pt;
-        UP(float, abt.data(), abt.size(), pt);
-        devABt[cls] = pt; ldt[cls] = lt;
-      }
-      c->ab_scale[cls] = gemm_scale(ab.data(), ab.size());
-    }
-    c->abclass[l] = cls;
-    D.AB = devAB[cls]; D.ldab = ldab[cls];
-    D.ABt = devABt[cls]; D.ldt = ldt[cls];
-    if (!D.ABt) c->small_ok = false;
-    D.amp = L.amplitude;
-    D.wxo = L.wfs_xoff; D.wyo = L.wfs_yoff; D.txo = L.tar_xoff; D.tyo = L.tar_yoff;
-    D.wox = (int)L.wfs_xoff; D.woy = (int)L.wfs_yoff; D.tox = (int)L.tar_xoff; D.toy = (int)L.tar_yoff;
-    if (!is_int(L.wfs_xoff) || !is_int(L.wfs_yoff)) s.wfs_all_int = 0;
-    if (!is_int(L.tar_xoff) || !is_int(L.tar_yoff)) s.tar_all_int = 0;
-    if (s.wfs_all_int && (D.wox < 0 || D.woy < 0 || D.wox + d->n > L.dim || D.woy + d->n > L.dim)) { aomarl_destroy(c); return fail("WFS window leaves screen %d", l); }
-    if (s.tar_all_int && (D.tox < 0 || D.toy < 0 || D.tox + d->pupdiam > L.dim || D.toy + d->pupdiam > L.dim)) { aomarl_destroy(c); return fail("target window leaves screen %d", l); }
-  }
-  s.screen_stride = off;
-  // DMs
-  c->ndm = s.ndm = d->ndm;
-  long long soff = 0; int coff = 0;
-  for (int k = 0; k < d->ndm; k++) {
-    const aomarl_dm_desc &M = d->dms[k];
-    DevDm &D = s.dms[k];
-    D.type = M.type; D.dim = M.dim; D.nact = M.nact; D.ss = M.influsize;
-    D.shape_off = soff;
-    soff += (M.type == AOMARL_DM_TT) ? 4 : (long long)M.dim * M.dim;   // TT: 2 commands (+pad)
-    D.com_off = coff; coff += M.nact;
-    if (M.type == AOMARL_DM_PZT) {
-      UP(float, M.influ, (size_t)M.nact * M.influsize * M.influsize, D.influ);
-      UP(int32_t, M.influpos, (size_t)M.ninflupos, D.influpos);
-      UP(int32_t, M.ninflu, (size_t)M.dim * M.dim, D.ninflu);
-      UP(int32_t, M.influstart, (size_t)M.dim * M.dim, D.influstart);
-      // bounds of the gather tables (a bad table would fault on the device)
-      long long tot = 0;
-      for (long long p = 0; p < (long long)M.dim * M.dim; p++) {
-        if (M.influstart[p] != tot || M.ninflu[p] < 0) { aomarl_destroy(c); return fail("DM %d: influstart/ninflu inconsistent", k); }
-        tot += M.ninflu[p];
-      }
-      if (tot != M.ninflupos) { aomarl_destroy(c); return fail("DM %d: sum(ninflu) != len(influpos)", k); }
-      for (long long q = 0; q < M.ninflupos; q++)
-        if (M.influpos[q] < 0 || M.influpos[q] >= M.nact * M.influsize * M.influsize) { aomarl_destroy(c); return fail("DM %d: influpos out of range", k); }
-      // ---- separable-lattice fast path: recover (i1, j1) of every actuator from the gather
-      // tables (first pixel that references sample 0 of its patch), check that all patches are
-      // one rank-1 profile and that the actuators sit on a regular lattice.
-      {
-        const int ss = M.influsize, ss2 = ss * ss, na = M.nact;
-        std::vector<int> i1(na, INT32_MIN), j1(na, INT32_MIN);
-        for (long long p = 0; p < (long long)M.dim * M.dim; p++)
-          for (int t = 0; t < M.ninflu[p]; t++) {
-            int pos = M.influpos[M.influstart[p] + t];
-            int act = pos / ss2, rem = pos % ss2, a = rem / ss, b = rem % ss;   // b: x offset
-            int x = (int)(p % M.dim) - b, y = (int)(p / M.dim) - a;
-            if (i1[act] == INT32_MIN) { i1[act] = x; j1[act] = y; }
-            else if (i1[act] != x || j1[act] != y) { i1[act] = INT32_MAX; }
-          }
-        bool ok = na > 0 && ss <= 128;
-        for (int a = 0; a < na && ok; a++) ok = (i1[a] != INT32_MIN && i1[a] != INT32_MAX);
-        // identical patches
-        for (int a = 1; a < na && ok; a++)
-          ok = memcmp(M.influ + (size_t)a * ss2, M.influ, sizeof(float) * ss2) == 0;
-        std::vector<float> prof(ss, 0.f);
-        if (ok) {
-          int cdx = 0; float best = 0.f;
-          for (int t = 0; t < ss; t++) if (M.influ[t * ss + t] > best) { best = M.influ[t * ss + t]; cdx = t; }
-          ok = best > 0.f;
-          if (ok) {
-            const float sc = 1.0f / sqrtf(best);
-            float mx = 0.f;
-            for (int t = 0; t < ss; t++) prof[t] = M.influ[t * ss + cdx] * sc;
-            for (int a = 0; a < ss; a++)
-              for (int b = 0; b < ss; b++) mx = fmaxf(mx, fabsf(M.influ[a * ss + b] - prof[a] * prof[b]));
-            ok = mx <= 2e-6f * best;
-          }
-        }
-        int pitch = 0, imin = INT32_MAX, jmin = INT32_MAX, imax = INT32_MIN, jmax = INT32_MIN;
-        if (ok) {
-          auto gcd = [](int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; };
-          for (int a = 0; a < na; a++) { imin = std::min(imin, i1[a]); jmin = std::min(jmin, j1[a]); imax = std::max(imax, i1[a]); jmax = std::max(jmax, j1[a]); }
-          for (int a = 0; a < na; a++) { pitch = gcd(pitch, i1[a] - imin); pitch = gcd(pitch, j1[a] - jmin); }
-          ok = pitch > 0 && ss <= 4 * pitch && (DMS_TX + ss - 1) / pitch + 2 <= DMS_GX && (DMS_TY + ss - 1) / pitch + 2 <= DMS_GY;
-        }
-        if (ok) {
-          const int gw = (imax - imin) / pitch + 1, gh = (jmax - jmin) / pitch + 1;
-          std::vector<int32_t> grid((size_t)gw * gh, -1);
-          for (int a = 0; a < na && ok; a++) {
-            int32_t &cell = grid[(size_t)((j1[a] - jmin) / pitch) * gw + (i1[a] - imin) / pitch];
-            if (cell != -1) ok = false;
-            cell = a;
-          }
-          if (ok) {
-            D.sep = 1; D.pitch = pitch; D.i1min = imin; D.j1min = jmin; D.gw = gw; D.gh = gh;
-            UP(int32_t, grid.data(), grid.size(), D.grid);
-            UP(float, prof.data(), prof.size(), D.prof);
-            if (k == 0) { c->h_grid = grid; c->h_prof = prof; }
-          }
-        }
-      }
-    } else if (M.type == AOMARL_DM_TT) {
-      if (M.nact != 2) { aomarl_destroy(c); return fail("tip-tilt DM must have 2 actuators"); }
-      UP(float, M.influ, (size_t)M.dim * M.dim * 2, D.influ);
-      if (k == 1) c->h_tt.assign(M.influ, M.influ + (size_t)M.dim * M.dim * 2);
-    } else {
-      aomarl_destroy(c);
-      return fail("DM %d: unknown type %d", k, M.type);
-    }
-    D.wxo = M.wfs_xoff; D.wyo = M.wfs_yoff; D.txo = M.tar_xoff; D.tyo = M.tar_yoff;
-    D.wox = (int)M.wfs_xoff; D.woy = (int)M.wfs_yoff; D.tox = (int)M.tar_xoff; D.toy = (int)M.tar_yoff;
-    if (!is_int(M.wfs_xoff) || !is_int(M.wfs_yoff)) s.wfs_all_int = 0;
-    if (!is_int(M.tar_xoff) || !is_int(M.tar_yoff)) s.tar_all_int = 0;
-    if (s.wfs_all_int && (D.wox < 0 || D.woy < 0 || D.wox + d->n > M.dim || D.woy + d->n > M.dim)) { aomarl_destroy(c); return fail("WFS window leaves DM %d", k); }
-    if (s.tar_all_int && (D.tox < 0 || D.toy < 0 || D.tox + d->pupdiam > M.dim || D.toy + d->pupdiam > M.dim)) { aomarl_destroy(c); return fail("target window leaves DM %d", k); }
-  }
-  s.shape_stride = soff;
-  if (coff != d->nactu) { aomarl_destroy(c); return fail("sum of DM actuators (%d) != nactu (%d)", coff, d->nactu); }
-  if (d->nslope != 2 * d->nvalid) { aomarl_destroy(c); return fail("nslope must be 2*nvalid"); }
-  s.nactu = d->nactu; s.nslope = d->nslope;
-  // target
-  s.tar_inv_lambda = 1.0f / d->tar_lambda; s.npsf = d->npsf; s.hw = d->strehl_halfwin;
-  std::vector<float> tw((size_t)d->npsf * 2);
-  for (int j = 0; j < d->npsf; j++) {
-    double a = 2.0 * M_PI * (double)j / (double)d->npsf;
-    tw[2 * j] = (float)cos(a); tw[2 * j + 1] = (float)sin(a);
-  }
-  UP(float, tw.data(), tw.size(), s.psf_tw);
-  double sp = 0.;
-  for (size_t p = 0; p < (size_t)d->pupdiam * d->pupdiam; p++) sp += d->spupil[p];
-  s.ref_peak = (float)(sp * sp);
-  c->gain = d->gain; c->delay = d->delay;
-  if (c->delay < 0.f || c->delay > 2.f) { aomarl_destroy(c); return fail("delay must be in [0, 2]"); }
-  // ---- fused frame kernel: the WFS tiles must BE the tiles of the pupil grid, at the same
-  // screen / DM pixels, the pupil must be binary
-  s.fused_ok = 0; s.ntiles = 0;
-  {
-    const int pd = d->pupdiam, pad = (d->n - pd) / 2;
-    bool ok = s.wfs_all_int && s.tar_all_int && d->ndm == 2 && d->dms[0].type == AOMARL_DM_PZT &&
-              d->dms[1].type == AOMARL_DM_TT && (d->nlayers == 1 || d->nlayers == 3) &&
-              d->strehl_halfwin == 8 && pd % 16 == 0 && pad >= 0 && d->n == pd + 2 * pad && d->nvalid <= 0xFFFF &&
-              (d->npsf & (d->npsf - 1)) == 0 && d->npsf <= 4096 && pd / 16 <= 256;
-    for (int l = 0; l < d->nlayers && ok; l++)
-      ok = s.layers[l].wox + pad == s.layers[l].tox && s.layers[l].woy + pad == s.layers[l].toy;
-    for (int k = 0; k < d->ndm && ok; k++)
-      ok = s.dms[k].wox + pad == s.dms[k].tox && s.dms[k].woy + pad == s.dms[k].toy;
-    for (int y = 0; y < pd && ok; y++)
-      for (int x = 0; x < pd && ok; x++) {
-        const float m = d->spupil[(size_t)y * pd + x];
-        ok = (m == 0.f || m == 1.f) && d->mpupil[(size_t)(y + pad) * d->n + x + pad] == m;
-      }
-    const int nt = pd / 16;
-    std::vector<int32_t> tsub((size_t)std::max(nt * nt, 1), -1);
-    std::vector<uint16_t> tmask((size_t)std::max(pd * nt, 1), 0);
-    if (ok) {
-      for (int y = 0; y < pd; y++)
-        for (int x = 0; x < pd; x++)
-          if (d->spupil[(size_t)y * pd + x] != 0.f) tmask[(size_t)y * nt + x / 16] |= (uint16_t)(1u << (x % 16));
-      for (int r = 0; r < nt; r++)
-        for (int t = 0; t < nt; t++) {
-          bool lit = false;
-          for (int yy = 0; yy < 16; yy++) lit = lit || tmask[(size_t)(16 * r + yy) * nt + t] != 0;
-          if (!lit) tsub[(size_t)r * nt + t] = -2;
-        }
-      for (int i = 0; i < d->nvalid && ok; i++) {
-        const int x0 = (sub[i] & 0xFFFF) - pad, y0 = (sub[i] >> 16) - pad;
-        ok = x0 >= 0 && y0 >= 0 && x0 % 16 == 0 && y0 % 16 == 0 && x0 < pd && y0 < pd;
-        if (ok) {
-          int32_t &cell = tsub[(size_t)(y0 / 16) * nt + x0 / 16];
-          ok = cell < 0;                 // one sub-aperture per tile (an unlit tile with a
-          cell = i;                      // sub-aperture is still imaged: zero flux, zero slopes)
-        }
-      }
-    }
-    if (ok) {
-      // tile_info: [15:0] sub-aperture, bit 16 lit, 17 every pixel lit, 18 valid sub-aperture
-      std::vector<int32_t> tinfo(tsub.size(), 0);
-      for (int r = 0; r < nt; r++)
-        for (int t = 0; t < nt; t++) {
-          const int32_t sb = tsub[(size_t)r * nt + t];
-          bool full = true;
-          for (int yy = 0; yy < 16; yy++) full = full && tmask[(size_t)(16 * r + yy) * nt + t] == 0xFFFF;
-          int32_t v = 0;
-          if (sb != -2) v |= 0x10000;
-          if (full) v |= 0x20000;
-          if (sb >= 0) { v |= 0x40000 | sb; v |= 0x10000; }     // an unlit tile with a sub-aperture is still imaged
-          tinfo[(size_t)r * nt + t] = v;
-        }
-      UP(int32_t, tinfo.data(), tinfo.size(), s.tile_info);
-      {
-        if (nt > 127) { aomarl_destroy(c); return fail("pupil too wide for the frame kernel's tile list"); }
-        std::vector<int32_t> linfo((size_t)nt * (nt + 8), 0), lcount(nt, 0);
-        for (int r = 0; r < nt; r++) {
-          int k = 0;
-          for (int t = 0; t < nt; t++)
-            if (tinfo[(size_t)r * nt + t] & 0x10000) linfo[(size_t)r * (nt + 8) + k++] = tinfo[(size_t)r * nt + t] | (t << 24);
-          lcount[r] = k;
-          for (int kk = k; kk < nt + 8; kk++) linfo[(size_t)r * (nt + 8) + kk] = k ? linfo[(size_t)r * (nt + 8) + k - 1] : 0;
-        }
-        UP(int32_t, linfo.data(), linfo.size(), s.lit_info);
-        UP(int32_t, lcount.data(), lcount.size(), s.lit_count);
-        // the same tiles in pairs (2 g, 2 g + 1): the frame kernel fetches the layer rows of a pair as whole
-        // 128-byte pieces
-        const int npm = (nt + 1) / 2 + 2;
-        std::vector<int32_t> pinfo((size_t)nt * npm * 2, 0), pcount(nt, 0);
-        for (int r = 0; r < nt; r++) {
-          int k = 0;
-          int32_t *row = &pinfo[(size_t)r * npm * 2];
-          for (int g = 0; 2 * g < nt; g++) {
-            const int ta = 2 * g, tb = 2 * g + 1 < nt ? 2 * g + 1 : 2 * g;
-            const int32_t va = tinfo[(size_t)r * nt + ta], vb = 2 * g + 1 < nt ? tinfo[(size_t)r * nt + tb] : 0;
-            if (!((va | vb) & 0x10000)) continue;
-            row[2 * k] = ((va & 0x10000) ? va : 0) | (ta << 24);
-            row[2 * k + 1] = ((vb & 0x10000) ? vb : 0) | (tb << 24);
-            k++;
-          }
-          pcount[r] = k;
-          for (int kk = k; kk < npm; kk++) {
-            row[2 * kk] = k ? row[2 * (k - 1)] : 0;
-            row[2 * kk + 1] = k ? row[2 * (k - 1) + 1] : 0;
-          }
-        }
-        UP(int32_t, pinfo.data(), pinfo.size(), s.pair_info);
-        UP(int32_t, pcount.data(), pcount.size(), s.pair_count);
-      }
-      {
-        std::vector<int32_t> order(nt), work(nt, 0);
-        for (int r = 0; r < nt; r++) {
-          order[r] = r;
-          for (int t = 0; t < nt; t++) {
-            const int32_t v = tinfo[(size_t)r * nt + t];
-            work[r] += (v & 0x10000) ? ((v & 0x40000) ? 4 : 1) : 0;   // a sub-aperture tile costs ~4x a bare one
-          }
-        }
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return work[a] > work[b]; });
-        UP(int32_t, order.data(), order.size(), s.stripe_order);
-      }
-      // PSF operand of the frame kernel for lane (q, c) of tile t: X = 16 t + 4 q + j (j = 0..3), column c of
-      // [cos 2 pi k X / npsf (k = 1..8) | sin 2 pi k X / npsf (k = 1..8)]; fp32 and [hi | lo] split-fp16 form
-      {
-        std::vector<_Float16> tw((size_t)nt * 64 * 8);
-        std::vector<float> twf((size_t)nt * 64 * 4);
-        for (int t = 0; t < nt; t++)
-          for (int lane = 0; lane < 64; lane++)
-            for (int j = 0; j < 4; j++) {
-              const int x = 16 * t + 4 * (lane >> 4) + j, cc = lane & 15;
-              const int k = cc < 8 ? cc + 1 : cc - 7;
-              const double th = 2.0 * M_PI * (double)(((long long)k * x) % d->npsf) / (double)d->npsf;
-              const float v = (float)(cc < 8 ? cos(th) : sin(th));
-              const _Float16 hi = (_Float16)v;
-              const _Float16 lo = (_Float16)(v - (float)hi);
-              _Float16 *o = &tw[((size_t)t * 64 + lane) * 8];
-              o[j] = hi; o[4 + j] = lo;
-              twf[((size_t)t * 64 + lane) * 4 + j] = v;
-            }
-        const _Float16 *dev = nullptr;
-        UP(_Float16, tw.data(), tw.size(), dev);
-        s.psf_tw_h = dev;
-        const float *devf = nullptr;
-        UP(float, twf.data(), twf.size(), devf);
-        s.psf_tw_f = devf;
-      }
-      {
-        // the four-product moment constants of every lane (aomarl_qf4_host.h), checked against M and S in double
-        float qtab[64 * 8];
-        if (!aomarl_qf4::build_table(qtab)) { aomarl_destroy(c); return fail("create: quadratic-form constants"); }
-        const float *qt = nullptr;
-        UP(float, qtab, 64 * 8, qt);
-        s.qf_tab = qt;
-      }
-      UP(uint16_t, tmask.data(), tmask.size(), s.tile_mask);
-      {
-        // tip-tilt planes as the frame kernel reads them (k_frame_wave: tvo): pupil pixel (y, 4 g + j)
-        const DevDm &T = s.dms[1];
-        std::vector<float> tp((size_t)pd * pd * 2);
-        for (int y = 0; y < pd; y++)
-          for (int g = 0; g < pd / 4; g++)
-            for (int j = 0; j < 4; j++) {
-              const size_t o = (size_t)(y + T.toy) * T.dim + T.tox + 4 * g + j;
-              float *dst = &tp[((size_t)y * (pd / 4) + g) * 8];
-              dst[j] = c->h_tt[2 * o]; dst[4 + j] = c->h_tt[2 * o + 1];
-            }
-        UP(float, tp.data(), tp.size(), s.tt_pk);
-      }
-      s.fused_ok = 1; s.ntiles = nt;
-      // stack-array DM evaluated from the command lattice inside the frame kernel
-      const DevDm &Z = s.dms[0];
-      s.otf_ok = 0;
-      if (Z.sep && Z.pitch > 0 && 16 % Z.pitch == 0) {
-        auto first = [&](int p0, int pmin) {
-          const int num = p0 - pmin - (Z.ss - 1);
-          return num >= 0 ? (num + Z.pitch - 1) / Z.pitch : -((-num) / Z.pitch);
-        };
-        s.otf_gx0 = first(Z.tox, Z.i1min); s.otf_gy0 = first(Z.toy, Z.j1min);
-        s.otf_xoff = Z.tox - (Z.i1min + Z.pitch * s.otf_gx0);
-        s.otf_yoff = Z.toy - (Z.j1min + Z.pitch * s.otf_gy0);
-        const int cnt = std::max((s.otf_xoff + 15) / Z.pitch + 1, (s.otf_yoff + 15) / Z.pitch + 1);
-        s.otf_nb = (cnt + 3) / 4; s.otf_tpn = 16 / Z.pitch;
-        s.otf_latw = (nt - 1) * s.otf_tpn + 4 * s.otf_nb;
-        s.otf_ok = (s.otf_nb >= 1 && s.otf_nb <= 2 && s.otf_xoff >= 0 && s.otf_yoff >= 0) ? 1 : 0;
-      }
-    }
-  }
-#undef UP
   *out = c;
   return 0;
 }

@@ -181,9 +181,7 @@ int aomarl_comp_image(aomarl_ctx *c, aomarl_state *st, int b, int n, int flags, 
   dim3 grid(gx, n), blk(256);
 #define SPOT(FB, NZ, WC) hipLaunchKernelGGL((k_wfs_spot<FB, NZ, WC>), grid, blk, 0, s, c->sys, ds, b, na, nd, cog)
 #define FAST(NL, NZ, WC) hipLaunchKernelGGL((k_wfs_spot_fast<NL, NZ, WC>), grid, blk, 0, s, c->sys, ds, b, cog)
-  const bool fast_ok = !from_buf && !na && !nd && !c->force_generic_spot && c->ndm == 2 &&
-                       c->sys.dms[0].type == AOMARL_DM_PZT && c->sys.dms[1].type == AOMARL_DM_TT &&
-                       (c->nlayers == 1 || c->nlayers == 3);
+  const bool fast_ok = !from_buf && !na && !nd && !c->force_generic_spot && c->production_layout;
   if (fast_ok) {
     if (c->nlayers == 1) {
       if (noise) { if (cube) FAST(1, true, true); else FAST(1, true, false); }
@@ -559,8 +557,7 @@ static int target_psf_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, bool f
   float *PEND = st->work + w.PEND + (size_t)b * (W * W + 4);
   DevState ds = dev_state(st);
   const bool tfast = c->sys.hw == 8 && !c->force_valu_target && !c->force_generic_target && !from_buf &&
-                     c->ndm == 2 && c->sys.dms[0].type == AOMARL_DM_PZT && c->sys.dms[1].type == AOMARL_DM_TT &&
-                     (c->nlayers == 1 || c->nlayers == 3);
+                     c->production_layout;
   if (tfast) {
     size_t smm = sizeof(float) * (4 * 16 * 65 + 4 * 2 * 256) + (c->sys.npsf <= 4096 ? sizeof(float) * 2 * c->sys.npsf : 0);
     if (c->nlayers == 1)

@@ -25,6 +25,7 @@ static const char *const g_arith_name[AR_N] = {
 // atmosphere: Fried-Clark extrusion on ring-buffered screens
 // =============================================================================================
 #include "aomarl_move_plan_host.h"    // RoundOps, RoundNext, MoveShift; SG_* and MOVE_SMALL_*: the limits the host plan tests
+#include "aomarl_create_plan_host.h"  // DMS_*: the tile of k_dm_shape_sep and the lattice cells it stages
 
 // Z[col][0..ns) = screen[stencil] - zref ; Z[col][ns..ns+n) = amplitude * N(0,1)
 // work item j of column col, for a ring origin (ox, oy) and an extrusion counter cnt given by the caller
@@ -494,10 +495,7 @@ __global__ __launch_bounds__(256) void k_dm_shape(DevSys sys, DevState st, int e
 
 // separable lattice fast path: tile of 64 x 32 pixels per block; the <= 9 x 8 lattice cells that
 // can reach the tile are staged in LDS; shape = sum_gy u(y - Yg) sum_gx u(x - Xg) C[gy][gx]
-#define DMS_TX 64
-#define DMS_TY 32
-#define DMS_GX 9
-#define DMS_GY 8
+// (DMS_TX / TY / GX / GY: aomarl_create_plan_host.h, the limits the creation plan tests)
 __global__ __launch_bounds__(256) void k_dm_shape_sep(DevSys sys, DevState st, int env_begin, int k,
                                                       const float *__restrict__ volts, int ldv) {
   __shared__ float sC[DMS_GY][DMS_GX + 1];
