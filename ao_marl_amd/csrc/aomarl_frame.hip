@@ -92,7 +92,9 @@ template <int NL, int NB, bool OTF, bool NOISE, bool WRITE_CUBE, bool HP>
 // the chunk a lane fetches XOR-ed with its row (lane = 8 row + (chunk ^ row)): the compute layout's ds_read_b128
 // (row c, chunk 4 h + q of tile h) then finds its 16 lanes in 16 different bank groups.
 #define FWD_BLK 1152                       // bytes from block 0 to block 1 of a layer image (FWD_IMG bytes: aomarl_dev.h)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3)))
+// (the slopes-only fp32 instantiations are held to 128 registers, the budget of four waves: beside a product's wave
+// and a scatter / gather block two frame waves have 256 of the SIMD's 512 -- what runs at a time is set by the LDS request)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((OTF && !HP && !NOISE && !WRITE_CUBE) ? 4 : 3, (OTF && !HP && !NOISE && !WRITE_CUBE) ? 4 : 3)))
 void k_frame_wave(DevSys sys, DevState st, int env_begin,
                                                     int env_count, int do_cog,
                                                     float *__restrict__ TR,
@@ -461,6 +463,149 @@ void k_frame_wave(DevSys sys, DevState st, int env_begin,
     }
   };
 
+  // Two fully lit sub-aperture tiles of a pair as ONE instruction block (the slopes-only fp32 instantiations; about nine
+  // pairs in ten at 40 x 40).  tile() is a strictly serial chain -- lattice product U, S behind it, the wait states in
+  // front of the phase arithmetic, slot reads, phases, transcendentals, PSF rows, stage 1 and stage 2 of the moments,
+  // wait states, ten dependent cross-lane steps, one LDS write -- and two calls in a row put tile B's independent work
+  // behind tile A's last reduction.  Here the two chains take turns, so that a matrix instruction never reads what one
+  // of the two matrix instructions in front of it wrote (the lattice and B's last two products apart: two chains each),
+  // one guard serves both tiles' phases, B's transcendentals sit between A's matrix instructions, and A's moments,
+  // reduction and LDS write between B's stage-1 instructions.  Every value comes from the same operations in the same
+  // order as in tile(): PA / PB take A's four K steps before B's, the packed sums A's terms before B's -- the same
+  // bits.  FW_SEQ pins the order written here (a scheduling barrier: the compiler's own interleave of independent
+  // matrix chains needed long s_nops of its own).
+#define FW_SEQ() __builtin_amdgcn_sched_barrier(0)
+  // where a lane puts a tile's row total: lanes 0, 16, 32 into the three moments, every other lane into the fourth word
+  // of the tile's entry, which nothing reads.  No branch in the block: with a divergent one at its end the compiler
+  // merged it with tile()'s and ran the two paths of the pair walk as one sequence, one's registers live through the other.
+  float *const qsel = reinterpret_cast<float *>(qmom) + ((c == 0 && q < 3) ? q : 3);
+  [[maybe_unused]] auto pair_block = [&](int ia, int ib, const FrameRaw<NL, OTF> &a, const FrameRaw<NL, OTF> &b, const float4 *sl) {
+    static_assert(!QF || PK, "the pair block is the packed fp32 form");
+    const int ta = (ia >> 24) & 0x7F, tb = (ib >> 24) & 0x7F;
+    // ---- A's tip-tilt planes out of its slot: in flight during the lattice products
+    const float4 xa = sl[lane], ya = sl[64 + lane];
+    // ---- lattice: U_A, U_B, S_A, S_B
+    f32x4 UA = Z4, UB = Z4;
+#pragma unroll
+    for (int kb = 0; kb < NB; kb++) {
+      const float la = latq[(q + 4 * kb) * latw + ta * tpn], lb = latq[(q + 4 * kb) * latw + tb * tpn];
+      UA = mfma16(jm_ok ? la : 0.f, Pyr[kb], UA);
+      UB = mfma16(jm_ok ? lb : 0.f, Pyr[kb], UB);
+    }
+    f32x4 SA = NP4, SB = NP4;
+#pragma unroll
+    for (int s = 0; s < NB; s++) {
+      SA = mfma16(Pxr[s], UA[s], SA);
+      SB = mfma16(Pxr[s], UB[s], SB);
+    }
+    // (matrix instructions have no side effect the compiler would order against the packed groups: without this it
+    // moves B's two down in front of B's phases)
+    asm volatile("" : "+v"(SA), "+v"(SB));
+    // ---- phases behind ONE guard.  B's tip-tilt planes are read where A's have been used up (the phases are where
+    // the block holds the most registers); A's layer sums cover the reads
+    const f32x2 XA01 = {xa.x, xa.y}, XA23 = {xa.z, xa.w}, YA01 = {ya.x, ya.y}, YA23 = {ya.z, ya.w};
+    PK_GUARD_MFMA();
+    f32x2 a01 = pk_fma_s(XA01, c0c0, pk_lo(SA)), a23 = pk_fma_s(XA23, c0c0, pk_hi(SA));
+    a01 = pk_fma_s(YA01, c1c1, a01); a23 = pk_fma_s(YA23, c1c1, a23);
+    FW_SEQ();
+    const float4 xb = sl[256 + lane], yb = sl[320 + lane];
+    FW_SEQ();
+#pragma unroll
+    for (int l = 0; l < NL; l++) {
+      const f32x2 la01 = {a.L[l][0], a.L[l][1]}, la23 = {a.L[l][2], a.L[l][3]};
+      a01 = pk_add(a01, la01); a23 = pk_add(a23, la23);
+    }
+    const f32x2 XB01 = {xb.x, xb.y}, XB23 = {xb.z, xb.w}, YB01 = {yb.x, yb.y}, YB23 = {yb.z, yb.w};
+    f32x2 b01 = pk_fma_s(XB01, c0c0, pk_lo(SB)), b23 = pk_fma_s(XB23, c0c0, pk_hi(SB));
+    b01 = pk_fma_s(YB01, c1c1, b01); b23 = pk_fma_s(YB23, c1c1, b23);
+#pragma unroll
+    for (int l = 0; l < NL; l++) {
+      const f32x2 lb01 = {b.L[l][0], b.L[l][1]}, lb23 = {b.L[l][2], b.L[l][3]};
+      b01 = pk_add(b01, lb01); b23 = pk_add(b23, lb23);
+    }
+    const f32x2 wa01 = pk_mul_s(a01, wil2), wa23 = pk_mul_s(a23, wil2), wb01 = pk_mul_s(b01, wil2), wb23 = pk_mul_s(b23, wil2);
+    const f32x2 ta01 = pk_mul_s(a01, til2), ta23 = pk_mul_s(a23, til2), tb01 = pk_mul_s(b01, til2), tb23 = pk_mul_s(b23, til2);
+    // variance sums: A's four terms, then B's (in-place forms: plain arithmetic is placed by the compiler where it
+    // likes, here behind the whole block, and the four phases then hold eight registers all the way)
+    pk_acc_add(sdp, a01); pk_acc_fma(sd2p, a01, a01);
+    pk_acc_add(sdp, a23); pk_acc_fma(sd2p, a23, a23);
+    pk_acc_add(sdp, b01); pk_acc_fma(sd2p, b01, b01);
+    pk_acc_add(sdp, b23); pk_acc_fma(sd2p, b23, b23);
+    FW_SEQ();
+    nfull += 2;
+    // the PSF operands of both tiles: read behind the phases, which hold the most registers, in flight during A's
+    // transcendentals
+    const float4 ca = sl[128 + lane], cb = sl[384 + lane];
+    // ---- A's sixteen transcendentals and its kx = 0 row sums.  B's sixteen go between the matrix instructions of A
+    // below, one pair behind each pair of those (all 32 up here held 134 registers; the limit is 128)
+    float wrA[4], wiA[4], arA[4], aiA[4], wrB[4], wiB[4], arB[4], aiB[4];
+    const float wa[4] = {wa01.x, wa01.y, wa23.x, wa23.y}, sa[4] = {ta01.x, ta01.y, ta23.x, ta23.y};
+    const float wb[4] = {wb01.x, wb01.y, wb23.x, wb23.y}, sb[4] = {tb01.x, tb01.y, tb23.x, tb23.y};
+#pragma unroll
+    for (int j = 0; j < 4; j++) { wrA[j] = __builtin_amdgcn_cosf(wa[j]); wiA[j] = __builtin_amdgcn_sinf(wa[j]); }
+#pragma unroll
+    for (int j = 0; j < 4; j++) { arA[j] = __builtin_amdgcn_cosf(sa[j]); aiA[j] = __builtin_amdgcn_sinf(sa[j]); }
+    {
+      const f32x2 ar01 = {arA[0], arA[1]}, ar23 = {arA[2], arA[3]}, ai01 = {aiA[0], aiA[1]}, ai23 = {aiA[2], aiA[3]};
+      PK_GUARD_TRANS();
+      const f32x2 sra = pk_add(ar01, ar23), sia = pk_add(ai01, ai23);
+      pk_acc_add(R0rp, sra); pk_acc_add(R0ip, sia);
+      PK_END_TO_MFMA();
+    }
+    // ---- matrix stream.  K step k of A's PSF rows beside stage 1 of A's moments: four accumulators in turn
+    const float csa[4] = {ca.x, ca.y, ca.z, ca.w}, csb[4] = {cb.x, cb.y, cb.z, cb.w};
+    f32x4 DrA = Z4, DiA = Z4;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      PA = mfma16(arA[k], csa[k], PA); PB = mfma16(aiA[k], csa[k], PB);
+      wrB[k] = __builtin_amdgcn_cosf(wb[k]); wiB[k] = __builtin_amdgcn_sinf(wb[k]);
+      FW_SEQ();
+      DrA = mfma16(wrA[k], qfk.h[k], DrA); DiA = mfma16(wiA[k], qfk.h[k], DiA);
+      arB[k] = __builtin_amdgcn_cosf(sb[k]); aiB[k] = __builtin_amdgcn_sinf(sb[k]);
+      FW_SEQ();
+    }
+    {   // B's kx = 0 row sums, behind A's in R0rp / R0ip
+      const f32x2 br01 = {arB[0], arB[1]}, br23 = {arB[2], arB[3]}, bi01 = {aiB[0], aiB[1]}, bi23 = {aiB[2], aiB[3]};
+      PK_GUARD_TRANS();
+      const f32x2 srb = pk_add(br01, br23), sib = pk_add(bi01, bi23);
+      pk_acc_add(R0rp, srb); pk_acc_add(R0ip, sib);
+      PK_END_TO_MFMA();
+    }
+    // B's PSF rows beside stage 2 of A: four accumulators in turn (with stage 1 of B in here as well -- six -- the block
+    // needs more than 128 registers)
+    f32x4 PrA = Z4, PiA = Z4;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      PA = mfma16(arB[k], csb[k], PA); PB = mfma16(aiB[k], csb[k], PB);
+      FW_SEQ();
+      PrA = mfma16(qfk.h[k], DrA[k], PrA); PiA = mfma16(qfk.h[k], DiA[k], PiA);
+      FW_SEQ();
+    }
+    // stage 1 of B, with A's moments, reduction and LDS write between its steps
+    f32x4 DrB = mfma16(wrB[0], qfk.h[0], Z4), DiB = mfma16(wiB[0], qfk.h[0], Z4);
+    FW_SEQ();
+    asm volatile("s_nop 7");                     // with the two instructions above: 10 wait states behind PiA
+    const QfTerms mA = qf_products(qfk, PrA, PiA);
+    DrB = mfma16(wrB[1], qfk.h[1], DrB); DiB = mfma16(wiB[1], qfk.h[1], DiB);
+    FW_SEQ();
+    float zA = qf_fold_rows(qfk, mA);
+    FW_SEQ();
+    DrB = mfma16(wrB[2], qfk.h[2], DrB); DiB = mfma16(wiB[2], qfk.h[2], DiB);
+    FW_SEQ();
+    zA = qf_fold_lanes(zA);
+    FW_SEQ();
+    DrB = mfma16(wrB[3], qfk.h[3], DrB); DiB = mfma16(wiB[3], qfk.h[3], DiB);
+    FW_SEQ();
+    qsel[4 * ta] = zA;
+    // stage 2 of B and its moments
+    f32x4 PrB = Z4, PiB = Z4;
+#pragma unroll
+    for (int k = 0; k < 4; k++) { PrB = mfma16(qfk.h[k], DrB[k], PrB); PiB = mfma16(qfk.h[k], DiB[k], PiB); }
+    PK_GUARD_MFMA();
+    const float zB = qf_fold_lanes(qf_fold_rows(qfk, qf_products(qfk, PrB, PiB)));
+    qsel[4 * tb] = zB;
+  };
+
   if constexpr (DMA) {
     // ---- the stripe's lit tiles in PAIRS (sys.pair_info): per pair ONE wait for everything fetched a pair ago, the
     // layer rows out of the wave's LDS image into registers, the block's shared data of both tiles into its slots,
@@ -519,8 +664,8 @@ void k_frame_wave(DevSys sys, DevState st, int env_begin,
     };
     int ia = pinfo[0], ib = pinfo[1];
     if (np > 0) { issue_shared(ia, ib, 0); issue(ia, ib); }
-    for (int k = 0; k < np; k++) {
-      const int ja = pinfo[2 * k + 2], jb = pinfo[2 * k + 3];
+    // head of a pair: its data out of the wave's image, the barrier, the fetches of the next pair; returns its slots
+    auto head = [&](int k, int ja, int jb) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // this pair's layer images, shared quarters and masks have landed
 #pragma unroll
       for (int l = 0; l < NL; l++) {
@@ -534,9 +679,32 @@ void k_frame_wave(DevSys sys, DevState st, int env_begin,
       float4 *slots = shb + (k & 1) * 512;
       __syncthreads();
       if (k + 1 < np) { issue_shared(ja, jb, (k + 1) & 1); issue(ja, jb); }
-      if (ia & FW_LIT) tile(ia, 0, A, A, dm, slots);
-      if (ib & FW_LIT) tile(ib, 0, B, B, dm, slots + 256);
-      ia = ja; ib = jb;
+      return slots;
+    };
+    // two fully lit sub-aperture tiles: the pair block (slopes-only fp32)
+    auto both_full = [&](int ia, int ib) {
+      constexpr int FW_PAIR = FW_LIT | FW_FULL | FW_SUB;
+      return QF && (ia & ib & FW_PAIR) == FW_PAIR && !dbg;
+    };
+    // Runs of such pairs -- the inside of a stripe -- are a loop of their own, one basic block: in one loop with the
+    // tile() path behind a branch the allocator kept the stripe's accumulators in other registers on the two sides
+    // and copied them back at the end of every pair (seventeen v_mov).
+    int k = 0;
+    while (k < np) {
+      if (both_full(ia, ib)) {
+        do {
+          const int ja = pinfo[2 * k + 2], jb = pinfo[2 * k + 3];
+          const float4 *slots = head(k, ja, jb);
+          if constexpr (QF) pair_block(ia, ib, A, B, slots);
+          ia = ja; ib = jb; k++;
+        } while (k < np && both_full(ia, ib));
+      } else {
+        const int ja = pinfo[2 * k + 2], jb = pinfo[2 * k + 3];
+        float4 *slots = head(k, ja, jb);
+        if (ia & FW_LIT) tile(ia, 0, A, A, dm, slots);
+        if (ib & FW_LIT) tile(ib, 0, B, B, dm, slots + 256);
+        ia = ja; ib = jb; k++;
+      }
     }
   } else {
   // The stripe's lit tiles, compact (sys.lit_info[r][k], tile index in bits 24..30; the entries past the last one

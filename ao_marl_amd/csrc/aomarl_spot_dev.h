@@ -365,20 +365,12 @@ __device__ __forceinline__ float dpp4e_mul(float a, float b) {
 __device__ __forceinline__ void dpp4e_fmac(float &acc, float a, float b) {
   asm volatile("v_fmac_f32_dpp %0, %1, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(acc) : "v"(a), "v"(b));
 }
-__device__ __forceinline__ float spot_qf_moments(const SpotQf &K, const float (&er)[4], const float (&ei)[4], const f32x4 z4) {
-  f32x4 Dr = z4, Di = z4;
-#pragma unroll
-  for (int s = 0; s < 4; s++) {
-    Dr = mfma16(er[s], K.h[s], Dr);              // (Er H')[y][a]
-    Di = mfma16(ei[s], K.h[s], Di);              // (Ei H')[y][a]
-  }
-  f32x4 Pr = z4, Pi = z4;
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    Pr = mfma16(K.h[r], Dr[r], Pr);              // (H'^T Er H')[b][a]
-    Pi = mfma16(K.h[r], Di[r], Pi);              // (H'^T Ei H')[b][a]
-  }
-  PK_GUARD_MFMA();
+// What follows the matrix products, in three pieces that can be called one by one (the frame kernel's pair block
+// puts the pieces of one tile between the matrix instructions of the other; spot_qf_moments runs them in a row):
+// qf_products: the lane's terms of the three sums from P.  Hand-kept group: the CALLER opens it with the guard that
+// covers the distance to the last matrix instruction that wrote Pr / Pi.
+struct QfTerms { f32x2 p0, py; float px; };
+__device__ __forceinline__ QfTerms qf_products(const SpotQf &K, const f32x4 Pr, const f32x4 Pi) {
   const f32x2 rl = pk_lo(Pr), rh = pk_hi(Pr), il = pk_lo(Pi), ih = pk_hi(Pi);
   // rows (r, r + 2) are a pair:  (Pi[0] Pr[2] - Pi[2] Pr[0],  Pi[1] Pr[3] - Pi[3] Pr[1]) . (-2 t_{2q}, -2 t_{2q+1});
   // columns (c, c ^ 2) are a pair: the lane's Pi against the partner's Pr, sign and t_k in the lane's constant.
@@ -397,15 +389,38 @@ __device__ __forceinline__ float spot_qf_moments(const SpotQf &K, const float (&
   pk_acc_fma(p0, ih, ih);
   dpp4e_fmac(px, Pr[3], Pi[3]);
   __builtin_amdgcn_sched_barrier(0);
-  const float s0 = p0.x + p0.y, tx = px * K.kx, ty = py.x + py.y;
+  return QfTerms{p0, py, px};
+}
+// qf_fold_rows: the three sums of a lane into ONE register, one sum per 16-lane row
+__device__ __forceinline__ float qf_fold_rows(const SpotQf &K, const QfTerms &m) {
+  const float s0 = m.p0.x + m.p0.y, tx = m.px * K.kx, ty = m.py.x + m.py.y;
   // (the second operand of the second fold is a register that is dead by now: rows 2, 3 of that fold -- row 3 of z --
   // are never read, and a swap of ty with itself would need a copy first)
-  float z = swap16_add(swap32_add(s0, tx), swap32_add(ty, p0.y));   // rows: s0, ty, tx, (unused)
+  return swap16_add(swap32_add(s0, tx), swap32_add(ty, m.p0.y));   // rows: s0, ty, tx, (unused)
+}
+// qf_fold_lanes: the row sums
+__device__ __forceinline__ float qf_fold_lanes(float z) {
   z += dpp_f<0xB1>(z);      // quad_perm [1,0,3,2]
   z += dpp_f<0x4E>(z);      // quad_perm [2,3,0,1]
   z += dpp_f<0x141>(z);     // row_half_mirror
   z += dpp_f<0x140>(z);     // row_mirror -> every lane holds its 16-lane row sum
   return z;
+}
+__device__ __forceinline__ float spot_qf_moments(const SpotQf &K, const float (&er)[4], const float (&ei)[4], const f32x4 z4) {
+  f32x4 Dr = z4, Di = z4;
+#pragma unroll
+  for (int s = 0; s < 4; s++) {
+    Dr = mfma16(er[s], K.h[s], Dr);              // (Er H')[y][a]
+    Di = mfma16(ei[s], K.h[s], Di);              // (Ei H')[y][a]
+  }
+  f32x4 Pr = z4, Pi = z4;
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    Pr = mfma16(K.h[r], Dr[r], Pr);              // (H'^T Er H')[b][a]
+    Pi = mfma16(K.h[r], Di[r], Pi);              // (H'^T Ei H')[b][a]
+  }
+  PK_GUARD_MFMA();
+  return qf_fold_lanes(qf_fold_rows(K, qf_products(K, Pr, Pi)));
 }
 // the two slopes of a sub-aperture from its moments (sum I, sum (X - 7.5) I / 2, -sum (Y - 7.5) I as
 // spot_qf_moments leaves them: the factors and the sign are part of the table's constants)
