@@ -1,7 +1,9 @@
 // aomarl_capi.hip -- C ABI (include/aomarl.h) over the gfx950 kernels in aomarl_kernels.hip: context, create / destroy,
 // setters and options here; the entry points by concern in aomarl_capi_atmos / _stages / _agents / _step / _extras /
 // _composites.hip, included at the end (one translation unit: the environment).  The one-pass frame kernel is a unit of
-// its own (aomarl_frame.hip, launched through aomarl_frame_host.h).  Mirror registration, the laser guide star, tomography,
+// its own (aomarl_frame.hip, launched through aomarl_frame_host.h), and so are the staged Shack-Hartmann and science-target
+// kernels (aomarl_wfs.hip, aomarl_target.hip, launched through aomarl_stage_host.h with a plan of
+// aomarl_stage_plan_host.h).  Mirror registration, the laser guide star, tomography,
 // the science field and the altitude mirrors are units of their own; what they may ask of a context is defined at the
 // very end (aomarl_env_host.h).
 // Host side only sequences kernel launches on the caller's stream; no device<->host copies after
@@ -9,6 +11,7 @@
 #include "aomarl_kernels.hip"
 #include "aomarl_env_host.h"
 #include "aomarl_frame_host.h"
+#include "aomarl_stage_host.h"
 #include "aomarl_create_plan_host.h"
 #include "aomarl_step_plan_host.h"
 
@@ -679,16 +682,6 @@ int env_trace_ready(aomarl_ctx *c, aomarl_state *st, int b, int n, int flags, vo
 
 int launch_inc_u32(uint32_t *p, int n, hipStream_t s) {
   hipLaunchKernelGGL(k_inc_u32, dim3((n + 255) / 256), dim3(256), 0, s, p, n);
-  LAUNCHCHK();
-  return 0;
-}
-int launch_strehl_reset(const DevSys &sys, const DevState &st, int env_begin, int n, hipStream_t s) {
-  hipLaunchKernelGGL(k_strehl_reset, dim3(n), dim3(256), 0, s, sys, st, env_begin);
-  LAUNCHCHK();
-  return 0;
-}
-int launch_strehl_fit_le(const DevSys &sys, const DevState &st, int env_begin, int n, hipStream_t s) {
-  hipLaunchKernelGGL(k_strehl_fit_le, dim3(n), dim3(64), 0, s, sys, st, env_begin);
   LAUNCHCHK();
   return 0;
 }

@@ -289,9 +289,7 @@ int aomarl_reset_strehl(aomarl_ctx *c, aomarl_state *st, int b, int n, void *str
   int rc = check_range(c, st, b, n);
   if (rc) return rc;
   if (n == 0) return 0;
-  hipLaunchKernelGGL(k_strehl_reset, dim3(n), dim3(256), 0, (hipStream_t)stream, c->sys, dev_state(st), b);
-  LAUNCHCHK();
-  return 0;
+  return launch_strehl_reset(c->sys, dev_state(st), b, n, (hipStream_t)stream);
 }
 
 // The rounds of a reset (refresh_screen: 2*dim extrusions along x, sign of deltax, atmosCompass.py:141-145).

@@ -112,9 +112,9 @@ static int frame_fused_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, int f
     if (!c->pipe.cmd_covers_commit)
       HIPCHK(hipStreamWaitEvent(c->psf_stream, c->pipe.ev_commit, 0));   // that parity's pending window has been committed
     // (its completion event rides on the dispatch, like the frame kernel's: one runtime call less per step)
-    hipExtLaunchKernelGGL(k_target_finish_mfma, dim3(n), dim3(256), 0, c->psf_stream, nullptr, c->pipe.ev_psf[slot], 0, c->sys, TR,
-                          TP, w.nblk, PEND, st->frame + b);
-    LAUNCHCHK();
+    const FinishEvents ev = {nullptr, c->pipe.ev_psf[slot]};
+    rc = launch_target_finish(FINISH_MFMA, c->sys, TR, TP, w.nblk, PEND, st->frame + b, n, c->psf_stream, &ev);
+    if (rc) return rc;
     c->pipe.psf_out[slot] = true;
     return 0;
   }
@@ -124,16 +124,14 @@ static int frame_fused_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, int f
     c->ev_frame_cur = ev_done; c->frame_marked = true;
     c->side_joined = false;
     HIPCHK(hipStreamWaitEvent(c->psf_stream, ev_done, 0));
-    hipExtLaunchKernelGGL(k_target_finish_mfma, dim3(n), dim3(256), 0, c->psf_stream, nullptr, c->capturing ? nullptr : c->ev_psf, 0,
-                          c->sys, TR, TP, w.nblk, PEND, st->frame + b);
-    LAUNCHCHK();
+    const FinishEvents ev = {nullptr, c->capturing ? nullptr : c->ev_psf};
+    rc = launch_target_finish(FINISH_MFMA, c->sys, TR, TP, w.nblk, PEND, st->frame + b, n, c->psf_stream, &ev);
+    if (rc) return rc;
     if (c->capturing) HIPCHK(hipEventRecord(c->ev_psf, c->psf_stream));       // (a captured dispatch carries no events)
     c->psf_side = true;
     return 0;
   }
-  hipLaunchKernelGGL(k_target_finish_mfma, dim3(n), dim3(256), 0, s, c->sys, TR, TP, w.nblk, PEND, st->frame + b);
-  LAUNCHCHK();
-  return 0;
+  return launch_target_finish(FINISH_MFMA, c->sys, TR, TP, w.nblk, PEND, st->frame + b, n, s);
 }
 
 /* refresh the stack-array planes of st->dm_shape from st->voltage (after deferred apply_control) */

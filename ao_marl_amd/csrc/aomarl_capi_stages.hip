@@ -163,43 +163,21 @@ int aomarl_comp_image(aomarl_ctx *c, aomarl_state *st, int b, int n, int flags, 
   rc = atmos_wait_pending(c, stream);
   if (rc) return rc;
   if (n == 0) return 0;
-  const bool from_buf = flags & AOMARL_IMG_FROM_PHASE_BUFFER;
-  const bool noise = (flags & AOMARL_IMG_NOISE) && c->sys.noise >= 0.f;
-  const bool cube = flags & AOMARL_IMG_WRITE_BINCUBE;
-  const int cog = (flags & AOMARL_IMG_COG) ? 1 : 0;
-  if (from_buf && !st->wfs_phase) return fail("comp_image: FROM_PHASE_BUFFER needs st->wfs_phase");
-  if (!from_buf && !c->sys.wfs_all_int)
-    return fail("comp_image: fused raytrace needs integer layer offsets; use raytrace_wfs + FROM_PHASE_BUFFER");
-  if (cube && !st->bincube) return fail("comp_image: WRITE_BINCUBE needs st->bincube");
-  if (!cube && !cog) return fail("comp_image: nothing to produce (neither bincube nor slopes)");
-  const int na = (flags & AOMARL_IMG_NO_ATMOS) ? 1 : 0, nd = (flags & AOMARL_IMG_NO_DMS) ? 1 : 0;
+  SpotQuery q;
+  q.from_buf = flags & AOMARL_IMG_FROM_PHASE_BUFFER;
+  q.noise = (flags & AOMARL_IMG_NOISE) && c->sys.noise >= 0.f;
+  q.cube = flags & AOMARL_IMG_WRITE_BINCUBE;
+  q.cog = flags & AOMARL_IMG_COG;
+  q.no_atmos = flags & AOMARL_IMG_NO_ATMOS; q.no_dms = flags & AOMARL_IMG_NO_DMS;
+  q.force_generic_spot = c->force_generic_spot; q.production_layout = c->production_layout;
+  q.nlayers = c->nlayers; q.nvalid = c->sys.nvalid; q.n = n;
+  q.has_wfs_phase = st->wfs_phase != nullptr; q.has_bincube = st->bincube != nullptr;
+  q.wfs_all_int = c->sys.wfs_all_int;
+  const SpotPlan p = plan_spot(q);
+  if (p.refusal != SPOT_OK) return fail("%s", spot_refusal_text(p.refusal));
   hipStream_t s = (hipStream_t)stream;
-  DevState ds = dev_state(st);
-  // persistent waves: enough blocks per environment to fill the chip ~2x (256 CUs x 32 waves)
-  int gx = (16384 + 4 * n - 1) / (4 * n);
-  gx = std::max(1, std::min(gx, (c->sys.nvalid + 3) / 4));
-  dim3 grid(gx, n), blk(256);
-#define SPOT(FB, NZ, WC) hipLaunchKernelGGL((k_wfs_spot<FB, NZ, WC>), grid, blk, 0, s, c->sys, ds, b, na, nd, cog)
-#define FAST(NL, NZ, WC) hipLaunchKernelGGL((k_wfs_spot_fast<NL, NZ, WC>), grid, blk, 0, s, c->sys, ds, b, cog)
-  const bool fast_ok = !from_buf && !na && !nd && !c->force_generic_spot && c->production_layout;
-  if (fast_ok) {
-    if (c->nlayers == 1) {
-      if (noise) { if (cube) FAST(1, true, true); else FAST(1, true, false); }
-      else { if (cube) FAST(1, false, true); else FAST(1, false, false); }
-    } else {
-      if (noise) { if (cube) FAST(3, true, true); else FAST(3, true, false); }
-      else { if (cube) FAST(3, false, true); else FAST(3, false, false); }
-    }
-  } else if (from_buf) {
-    if (noise) { if (cube) SPOT(true, true, true); else SPOT(true, true, false); }
-    else { if (cube) SPOT(true, false, true); else SPOT(true, false, false); }
-  } else {
-    if (noise) { if (cube) SPOT(false, true, true); else SPOT(false, true, false); }
-    else { if (cube) SPOT(false, false, true); else SPOT(false, false, false); }
-  }
-#undef SPOT
-#undef FAST
-  LAUNCHCHK();
+  rc = launch_spot(p, c->sys, dev_state(st), b, s);                // (aomarl_wfs.hip)
+  if (rc) return rc;
   hipLaunchKernelGGL(k_inc_u32, dim3((n + 255) / 256), dim3(256), 0, s, st->frame + b, n);
   LAUNCHCHK();
   return 0;
@@ -210,9 +188,7 @@ int aomarl_do_centroids(aomarl_ctx *c, aomarl_state *st, int b, int n, void *str
   if (rc) return rc;
   if (!st->bincube) return fail("do_centroids needs st->bincube");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(k_cog, dim3((c->sys.nvalid + 3) / 4, n), dim3(256), 0, (hipStream_t)stream, c->sys, dev_state(st), b);
-  LAUNCHCHK();
-  return 0;
+  return launch_cog(c->sys, dev_state(st), b, n, (hipStream_t)stream);
 }
 
 int aomarl_slopes_geom(aomarl_ctx *c, aomarl_state *st, int b, int n, void *stream) {
@@ -220,9 +196,7 @@ int aomarl_slopes_geom(aomarl_ctx *c, aomarl_state *st, int b, int n, void *stre
   if (rc) return rc;
   if (!st->wfs_phase) return fail("slopes_geom needs st->wfs_phase");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(k_slopes_geom, dim3((c->sys.nvalid + 3) / 4, n), dim3(256), 0, (hipStream_t)stream, c->sys, dev_state(st), b);
-  LAUNCHCHK();
-  return 0;
+  return launch_slopes_geom(c->sys, dev_state(st), b, n, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- controller
@@ -551,44 +525,19 @@ static int target_psf_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, bool f
   if (psf_wait_pending(c, stream)) return 1;
   hipStream_t s = (hipStream_t)stream;
   Work w = work_layout(c, st->nenv);
-  const int W = 2 * c->sys.hw, RB = 256 / W;
+  const int W = 2 * c->sys.hw;
   float *TR = st->work + w.TR + (size_t)b * c->sys.pupdiam * W * 2;
   float *TP = st->work + w.TPART + (size_t)b * w.nblk * 4;
   float *PEND = st->work + w.PEND + (size_t)b * (W * W + 4);
-  DevState ds = dev_state(st);
-  const bool tfast = c->sys.hw == 8 && !c->force_valu_target && !c->force_generic_target && !from_buf &&
-                     c->production_layout;
-  if (tfast) {
-    size_t smm = sizeof(float) * (4 * 16 * 65 + 4 * 2 * 256) + (c->sys.npsf <= 4096 ? sizeof(float) * 2 * c->sys.npsf : 0);
-    if (c->nlayers == 1)
-      hipLaunchKernelGGL(k_target_rows_fast<1>, dim3(w.nblk, n), dim3(256), smm, s, c->sys, ds, b, TR, TP, w.nblk);
-    else
-      hipLaunchKernelGGL(k_target_rows_fast<3>, dim3(w.nblk, n), dim3(256), smm, s, c->sys, ds, b, TR, TP, w.nblk);
-    LAUNCHCHK();
-    hipLaunchKernelGGL(k_target_finish_mfma, dim3(n), dim3(256), 0, s, c->sys, TR, TP, w.nblk, PEND, (uint32_t *)nullptr);
-    LAUNCHCHK();
-    return 0;
-  }
-  if (c->sys.hw == 8 && !c->force_valu_target) {
-    size_t smm = sizeof(float) * (2 * 16 * 65 + 4 * 2 * 256) + (c->sys.npsf <= 4096 ? sizeof(float) * 2 * c->sys.npsf : 0);
-    if (from_buf)
-      hipLaunchKernelGGL(k_target_rows_mfma<true>, dim3(w.nblk, n), dim3(256), smm, s, c->sys, ds, b, TR, TP, w.nblk);
-    else
-      hipLaunchKernelGGL(k_target_rows_mfma<false>, dim3(w.nblk, n), dim3(256), smm, s, c->sys, ds, b, TR, TP, w.nblk);
-    LAUNCHCHK();
-    hipLaunchKernelGGL(k_target_finish_mfma, dim3(n), dim3(256), 0, s, c->sys, TR, TP, w.nblk, PEND, (uint32_t *)nullptr);
-    LAUNCHCHK();
-    return 0;
-  }
-  size_t sm = sizeof(float) * (2 * RB * TGT_XC + 3 * 256) + (c->sys.npsf <= 4096 ? sizeof(float) * 2 * c->sys.npsf : 0);
-  if (from_buf)
-    hipLaunchKernelGGL(k_target_rows<true>, dim3(w.nblk, n), dim3(256), sm, s, c->sys, ds, b, TR, TP, w.nblk);
-  else
-    hipLaunchKernelGGL(k_target_rows<false>, dim3(w.nblk, n), dim3(256), sm, s, c->sys, ds, b, TR, TP, w.nblk);
-  LAUNCHCHK();
-  hipLaunchKernelGGL(k_target_finish, dim3(n), dim3(256), 0, s, c->sys, TR, TP, w.nblk, PEND);
-  LAUNCHCHK();
-  return 0;
+  TargetQuery q;
+  q.hw = c->sys.hw; q.npsf = c->sys.npsf; q.pupdiam = c->sys.pupdiam; q.nlayers = c->nlayers;
+  q.from_buf = from_buf; q.production_layout = c->production_layout;
+  q.force_valu_target = c->force_valu_target; q.force_generic_target = c->force_generic_target;
+  q.nblk = w.nblk; q.n = n;
+  const TargetPlan p = plan_target(q);
+  const int rc = launch_target_rows(p, c->sys, dev_state(st), b, TR, TP, s);       // (aomarl_target.hip)
+  if (rc) return rc;
+  return launch_target_finish(p.finish, c->sys, TR, TP, p.nblk, PEND, nullptr, n, s);
 }
 
 int aomarl_target_psf(aomarl_ctx *c, aomarl_state *st, int b, int n, void *stream) {
@@ -612,16 +561,12 @@ int aomarl_comp_strehl(aomarl_ctx *c, aomarl_state *st, int b, int n, void *stre
   Work w = work_layout(c, st->nenv);
   const int W = 2 * c->sys.hw;
   float *PEND = st->work + w.PEND + (size_t)b * (W * W + 4);
-  hipLaunchKernelGGL(k_strehl_commit, dim3(n), dim3(256), 0, (hipStream_t)stream, c->sys, dev_state(st), b, PEND);
-  LAUNCHCHK();
-  return 0;
+  return launch_strehl_commit(c->sys, dev_state(st), b, n, PEND, (hipStream_t)stream);
 }
 
 int aomarl_strehl_fit(aomarl_ctx *c, aomarl_state *st, int b, int n, void *stream) {
   if (!c || !st) return fail("strehl_fit: null ctx/state");
   if (b < 0 || n < 0 || b + n > st->nenv || !st->strehl || !st->le_img) return fail("strehl_fit: bad range / state");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(k_strehl_fit_le, dim3(n), dim3(64), 0, (hipStream_t)stream, c->sys, dev_state(st), b);
-  LAUNCHCHK();
-  return 0;
+  return launch_strehl_fit_le(c->sys, dev_state(st), b, n, (hipStream_t)stream);
 }

@@ -30,11 +30,9 @@ AOMARL_LOCAL int env_refuse_busy(const char *who, const aomarl_ctx *c);
 // voltages ("defer_dm_shape") -- those shapes
 AOMARL_LOCAL int env_trace_ready(aomarl_ctx *c, aomarl_state *st, int b, int n, int flags, void *stream);
 
-// kernels of the environment on a unit's own buffers (a kernel is launched from the unit that defines it):
-// k_inc_u32 on p[0 .. n); k_strehl_reset / k_strehl_fit_le on the n records and long-exposure sums from env_begin of st
+// a kernel of the environment on a unit's own buffer (a kernel is launched from the unit that defines it): k_inc_u32 on
+// p[0 .. n)
 AOMARL_LOCAL int launch_inc_u32(uint32_t *p, int n, hipStream_t s);
-AOMARL_LOCAL int launch_strehl_reset(const DevSys &sys, const DevState &st, int env_begin, int n, hipStream_t s);
-AOMARL_LOCAL int launch_strehl_fit_le(const DevSys &sys, const DevState &st, int env_begin, int n, hipStream_t s);
 
 // ---- the science field (aomarl_field.hip) as aomarl_field_attach_mirrors / _detach_mirrors (aomarl_mcao.hip) see it.
 // base: planes, nmirrors, stride and dim of the attached object (FieldMirArgs, aomarl_field_host.h); off: the

@@ -4,6 +4,7 @@
 // finish reuses psf_window_fit, fit_axis_gain and strehl_commit_body (aomarl_trace_dev.h) on the field's own buffers.  The
 // host half is aomarl_field_host.h.
 #include "aomarl_env_host.h"
+#include "aomarl_stage_host.h"        // launch_strehl_reset, launch_strehl_fit_le (aomarl_target.hip) on the field's buffers
 #include "aomarl_trace_dev.h"
 #include "aomarl_field_host.h"
 #include "aomarl_mcao_sample.h"

@@ -1,5 +1,6 @@
 // aomarl_host.h -- host-side pieces shared by the translation units of libaomarl_hip.so (aomarl_capi.hip: context,
-// frame / atmosphere / control kernels and their entry points; aomarl_capi_dmreg.hip, aomarl_lgs.hip, aomarl_tomo.hip,
+// atmosphere / control kernels and their entry points; aomarl_frame.hip, aomarl_wfs.hip, aomarl_target.hip: the frame
+// kernel and the staged sensor and target kernels, launched through aomarl_frame_host.h / aomarl_stage_host.h; aomarl_capi_dmreg.hip, aomarl_lgs.hip, aomarl_tomo.hip,
 // aomarl_field.hip, aomarl_mcao.hip: what traces on a context, through aomarl_env_host.h; aomarl_denoise.hip: the denoiser;
 // aomarl_denoise_train.hip: its training step; aomarl_sac.hip: the learner's update and the grouped GEMM; aomarl_roket.hip: the ROKET filter bank; aomarl_psfrec.hip: the PSF reconstruction; aomarl_groot.hip: the GROOT covariance model; aomarl_modopti.hip: the modal-gain filter bank; aomarl_predictor.hip: the modal predictor).  Not part of the C ABI: hidden visibility.
 #pragma once

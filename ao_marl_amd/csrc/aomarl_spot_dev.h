@@ -1,7 +1,7 @@
 // aomarl_spot_dev.h -- the device functions the one-pass frame kernel (aomarl_frame.hip) shares with the environment's
-// other kernels (aomarl_kernels.hip: k_wfs_spot, k_wfs_spot_fast, the target kernels; aomarl_gemm_nt.h): the split-fp16
-// operand helpers, the unaligned 4-float loads and the Shack-Hartmann spot of one sub-aperture on the matrix cores.
-// Each is the one text both units compile.
+// other kernels (aomarl_wfs.hip: k_wfs_spot, k_wfs_spot_fast; aomarl_target.hip: the target kernels; aomarl_kernels.hip:
+// aomarl_gemm_nt.h): the split-fp16 operand helpers, the unaligned 4-float loads and the Shack-Hartmann spot of one
+// sub-aperture on the matrix cores.  Each is the one text every unit compiles.
 #pragma once
 #include "aomarl_dev.h"
 

@@ -1,6 +1,6 @@
-// aomarl_trace_dev.h -- the device functions the environment's kernels (aomarl_kernels.hip) share with the translation
-// units that trace or finish a PSF on the context's description: aomarl_capi_dmreg.hip, aomarl_lgs.hip, aomarl_tomo.hip,
-// aomarl_field.hip.  Each is the one text every caller compiles; a unit that switches floating-point contraction off
+// aomarl_trace_dev.h -- the device functions the environment's kernels (aomarl_kernels.hip, aomarl_wfs.hip,
+// aomarl_target.hip) share with the translation units that trace or finish a PSF on the context's description:
+// aomarl_capi_dmreg.hip, aomarl_lgs.hip, aomarl_tomo.hip, aomarl_field.hip.  Each is the one text every caller compiles; a unit that switches floating-point contraction off
 // includes this header in front of its pragma, so that these keep the default contraction wherever they are inlined.
 #pragma once
 #include "aomarl_dev.h"

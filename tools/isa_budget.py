@@ -59,8 +59,9 @@ def main():
     ap.add_argument("--kernel", default=r"_Z12k_frame_waveILi3ELi1ELb1ELb0ELb0ELb0EE")
     ap.add_argument("--asm", default=None)
     ap.add_argument("--source", default="aomarl_frame.hip",
-                    help="translation unit under ao_marl_amd/csrc (default: the frame kernel's; aomarl_capi.hip is the rest of "
-                         "the environment; aomarl_capi_dmreg.hip, aomarl_lgs.hip, aomarl_tomo.hip, aomarl_field.hip and "
+                    help="translation unit under ao_marl_amd/csrc (default: the frame kernel's; aomarl_wfs.hip and "
+                         "aomarl_target.hip hold the staged Shack-Hartmann and science-target kernels, aomarl_capi.hip is the "
+                         "rest of the environment; aomarl_capi_dmreg.hip, aomarl_lgs.hip, aomarl_tomo.hip, aomarl_field.hip and "
                          "aomarl_mcao.hip are units of their own, like the denoiser, the learner and the rest of csrc/Makefile's "
                          "UNITS)")
     ap.add_argument("--lines", action="store_true", help="print every instruction with its category")
