@@ -14,6 +14,7 @@
 #include "aomarl_stage_host.h"
 #include "aomarl_create_plan_host.h"
 #include "aomarl_step_plan_host.h"
+#include "aomarl_order_host.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -65,11 +66,8 @@ struct aomarl_ctx {
   // "prefetch_atmos": the composite moves the atmosphere of the NEXT frame on a side stream as soon
   // as this frame's image kernels are done, so the extrusion chain runs beside do_control / the
   // agents / next_part_two instead of in front of the next image
-  bool prefetch_atmos = false, premoved = false;
-  // prefetch: the side stream has not yet waited for the frame kernel that reads the screens (ev_frame): the
-  // first kernel that WRITES them does (ExtrudeRun::launch); gather and GEMM of the first round run beside it
-  bool frame_wait_pending = false;
-  bool screens_dirty_main = true;       // the screens / origins were last written on the caller's stream
+  bool prefetch_atmos = false;
+  SideOrder order;                 // how the side streams stand against the caller's stream (aomarl_order_host.h)
   // power-of-two scales of the static matrices for the split-f16 GEMM (gemm_scale)
   float cmat_scale = 1.f, v2m_scale = 1.f, m2v_scale = 1.f, s2m_scale = 1.f, ab_scale[AOMARL_MAX_LAYERS] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
   // "subpixel_flow" (experiment, profiles/r03_subpixel_flow.txt): the fractional remainder of the wind
@@ -80,9 +78,8 @@ struct aomarl_ctx {
   // "graph_step": aomarl_env_step as a HIP graph (captured once per distinct launch sequence -- extrusion plan,
   // ring position, buffer addresses --, replayed afterwards: one hipGraphLaunch instead of ~25 launches and ~8
   // event operations per step).  capturing: the body is being recorded (no timed / event-carrying dispatch, the
-  // side streams fork from and join the caller's stream inside the graph).  side_joined: the caller's stream
-  // has already waited for everything issued on the side streams (the waits for ev_moved / ev_psf are skipped)
-  bool graph_step = false, capturing = false, side_joined = false, fork_recorded = false;
+  // side streams fork from and join the caller's stream inside the graph)
+  bool graph_step = false, capturing = false;
   hipEvent_t ev_fork = nullptr;
   struct StepGraph { std::vector<long long> key; hipGraphExec_t exec; hipGraph_t graph; unsigned long long arith[AR_N]; int fw_variant[6]; };
   std::vector<StepGraph> graphs;
@@ -102,13 +99,9 @@ struct aomarl_ctx {
   size_t fw_ev_used = 0;
   std::vector<hipEvent_t> fw_ev_retired;    // timing events a frame in flight still carries as its "done" mark (fw_ev_rewind)
   hipStream_t atm_stream = nullptr, psf_stream = nullptr;
+  // (the screens' readers are marked with ev_frame or with the closing event of a timed frame launch: an event
+  // record is a barrier packet of its own on the queue, 3-5 us of the step each -- one per frame, not three)
   hipEvent_t ev_frame = nullptr, ev_moved = nullptr, ev_psf = nullptr;
-  // the event the screens' readers were last marked with on the caller's stream (ev_frame, or the closing
-  // event of a timed frame launch: an event record is a barrier packet of its own on the queue, 3-5 us of
-  // the step each -- one per frame, not three); frame_marked: recorded by aomarl_frame_fused and nothing
-  // launched on that stream since (the composites' prefetch reuses it)
-  hipEvent_t ev_frame_cur = nullptr;
-  bool frame_marked = false;
   // frame pipeline (aomarl_set_frame_pipeline): frames on a stream of their own, one step ahead of the chains
   struct FramePipe {
     bool have_twin = false, active = false;
@@ -125,16 +118,8 @@ struct aomarl_ctx {
     size_t snap_ints = 0;
     unsigned long long steps = 0, overlapped = 0, behind = 0;
   } pipe;
-  int32_t *snap_target = nullptr;        // a pipelined move: where the scatter kernels also write the origins they advance
   bool pipe_enabled = true;              // "frame_pipeline": 0 = plain call order although a twin is set
   bool pipe_internal = false;            // check_range: the pipelined step itself is calling
-  // first write of a prefetched move: behind the OLDER frame in flight (ev_frame_prev) when the lines the move
-  // rewrites are outside the frame kernel's windows (GroupPlan::overlap, decided per group), else behind the newest
-  hipEvent_t ev_frame_prev = nullptr;
-  bool need_prev = false;
-  bool psf_side = false;                // a k_target_finish_mfma launched on the side stream may still run
-  const float *pre_screens = nullptr;
-  int pre_b = 0, pre_n = 0;
   // controller matrices
   float *cmat = nullptr;           // [nactu][ld_s]
   int ld_cmat = 0;
@@ -181,10 +166,11 @@ struct aomarl_ctx {
 static int pipe_drop(aomarl_ctx *c, void *stream);
 static void rp_free(aomarl_ctx *c);
 // Start the timing events over.  The closing event of a timed frame launch doubles as that frame's "readers are
-// done" mark (pipe.ev_done_cur / ev_frame_cur / ev_frame_prev): one that a frame in flight still carries must not be
+// done" mark (pipe.ev_done_cur, and what the ledger holds): one that a frame in flight still carries must not be
 // re-recorded by a later launch, so it is retired (it stays valid for whoever waits on it) and replaced.
 static int fw_ev_rewind(aomarl_ctx *c) {
-  const hipEvent_t held[4] = {c->pipe.ev_done_cur[0], c->pipe.ev_done_cur[1], c->ev_frame_cur, c->ev_frame_prev};
+  void *held[4] = {c->pipe.ev_done_cur[0], c->pipe.ev_done_cur[1], nullptr, nullptr};
+  c->order.held_events(held + 2);
   for (size_t i = 0; i < c->fw_ev.size(); i++)
     for (int k = 0; k < 4; k++)
       if (held[k] && c->fw_ev[i] == held[k]) {

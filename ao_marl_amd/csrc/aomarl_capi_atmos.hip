@@ -27,40 +27,36 @@ static int side_stream(aomarl_ctx *c) {
     }
     c->atm_stream = g_atm[dev]; c->psf_stream = g_psf[dev];
     HIPCHK(hipEventCreateWithFlags(&c->ev_frame, hipEventDisableTiming));
-    c->ev_frame_cur = c->ev_frame;
+    c->order.handles_created(c->ev_frame);
     HIPCHK(hipEventCreateWithFlags(&c->ev_moved, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_psf, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
   }
   return 0;
 }
-// everything that reads (or overwrites) the pending PSF window on `stream` waits for a finish kernel
-// that may still be running on the side stream
+// the queue the ledger of the side streams (c->order, aomarl_order_host.h) issues its waits and records through
+struct HipOrderQueue {
+  const char *site;                     // the function that issues: a failure's text names it
+  hipError_t err = hipSuccess;          // of the operation that failed
+  explicit HipOrderQueue(const char *site_) : site(site_) {}
+  int wait(void *stream, void *event) {
+    err = hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)event, 0);
+    return err == hipSuccess ? 0 : fail("hipStreamWaitEvent failed: %s (%s, %s)", hipGetErrorString(err), site, __FILE__);
+  }
+  int record(void *event, void *stream) {
+    err = hipEventRecord((hipEvent_t)event, (hipStream_t)stream);
+    return err == hipSuccess ? 0 : fail("hipEventRecord failed: %s (%s, %s)", hipGetErrorString(err), site, __FILE__);
+  }
+};
 static int psf_wait_pending(aomarl_ctx *c, void *stream) {
-  if (c->psf_side && !c->side_joined) HIPCHK(hipStreamWaitEvent((hipStream_t)stream, c->ev_psf, 0));
-  c->psf_side = false;
-  return 0;
+  HipOrderQueue q(__func__);
+  return c->order.psf_join(q, stream, c->ev_psf);
 }
 
 // ---------------------------------------------------------------- atmosphere
-// A prefetched move_atmos may still be running on the side stream: everything that touches the
-// screens on `stream` waits for it first.
 static int atmos_wait_pending(aomarl_ctx *c, void *stream) {
-  if (c->premoved && !c->side_joined) HIPCHK(hipStreamWaitEvent((hipStream_t)stream, c->ev_moved, 0));
-  return 0;
-}
-
-// the first kernel of a prefetched move that WRITES ring lines waits for the readers of the screens: for the OLDER
-// frame in flight when the group's plan says the move may run beside the newest (overlap), else for the newest
-static int first_write_wait(aomarl_ctx *c, hipStream_t s, bool overlap) {
-  if (s != c->atm_stream) return 0;
-  if (overlap && c->ev_frame_prev) {
-    if (c->need_prev) { HIPCHK(hipStreamWaitEvent(s, c->ev_frame_prev, 0)); c->need_prev = false; }
-  } else if (c->frame_wait_pending) {
-    HIPCHK(hipStreamWaitEvent(s, c->ev_frame_cur, 0));
-    c->frame_wait_pending = false; c->need_prev = false;
-  }
-  return 0;
+  HipOrderQueue q(__func__);
+  return c->order.move_join(q, stream, c->ev_moved);
 }
 
 // the one place that reads the move plan's facts off the context
@@ -91,15 +87,16 @@ struct ExtrudeRun {
   RoundCarry carry = {false, 0};
   int nsp = 0; float pscale = 1.f;   // what the last PRODUCT left for its scatter: split-K partial tiles and their factor
   int pick_n = 0;            // > 0: the products take the tile and k split a range of pick_n environments would get
-  bool overlap = false;      // the group's verdict (first_write_wait)
+  bool overlap = false;      // the group's verdict (SideOrder::ring_write)
   hipEvent_t ride_ev = nullptr;      // the event a whole-batch move's last launch may carry on its dispatch ...
   bool rode = false;                 // ... and whether it did
   // ordered = false: the caller has ordered the stream behind every reader of the screens (reset)
-  ExtrudeRun(aomarl_ctx *c_, aomarl_state *st_, int b_, int n_, void *stream, bool ordered_ = true)
+  // origin_snap_ (a pipelined move): where the scatter kernels also write the origins they advance
+  ExtrudeRun(aomarl_ctx *c_, aomarl_state *st_, int b_, int n_, void *stream, bool ordered_ = true, int32_t *origin_snap_ = nullptr)
       : c(c_), st(st_), b(b_), n(n_), s((hipStream_t)stream), ordered(ordered_) {
     w = work_layout(c, st->nenv);
     ds = dev_state(st);
-    if (ordered) ds.origin_snap = c->snap_target;
+    ds.origin_snap = origin_snap_;
     // the range's own part of every work area (columns are numbered from the range's first environment):
     // two ranges may run side by side on two streams
     const size_t col0 = (size_t)b * (c->nlayers > 0 ? c->nlayers : 1), ncols = (size_t)n * (c->nlayers > 0 ? c->nlayers : 1);
@@ -113,9 +110,9 @@ struct ExtrudeRun {
     const int ncol = n * ops.nops;
     const int dimc = L.ref >= 0 ? c->dim[L.ref] : 0, nsc = L.ref >= 0 ? c->ns[L.ref] : 0;
     if (L.is_write && ordered) {
-      int wrc = first_write_wait(c, s, overlap);
+      HipOrderQueue q(__func__);
+      int wrc = c->order.ring_write(q, s, c->atm_stream, overlap);
       if (wrc) return wrc;
-      if (s != c->atm_stream) c->screens_dirty_main = true;
     }
     // (the last launch of a whole-batch move carries the caller's "moved" event on its dispatch: no marker packet
     // of its own between the move and the frame kernel that waits for it)
@@ -188,8 +185,9 @@ struct MoveDone { bool complete, rode; };
 
 // one frame's move of [b, b + n): group by group (aomarl_move_plan_host.h), each group's rounds or its one small launch
 static int move_atmos_now(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accumx, float *accumy, void *stream,
-                          hipEvent_t ride_ev, MoveDone *done) {
+                          hipEvent_t ride_ev, MoveDone *done, int32_t *origin_snap = nullptr) {
   const AtmosFacts f = atmos_facts(c);
+  const bool older = c->order.older_frame_in_flight();
   const int nl = f.nlayers;
   MoveDone d = {true, false};
   for (int e = b; e < b + n;) {
@@ -198,12 +196,12 @@ static int move_atmos_now(aomarl_ctx *c, aomarl_state *st, int b, int n, float *
       for (int l = 0; l < nl; l++) { c->frac_x[l] = g.fx[l]; c->frac_y[l] = g.fy[l]; }
     e += g.n;
     // frame pipeline: may this group's move run beside the older frame in flight?
-    const GroupPlan gp = group_plan(g.k, f, c->ev_frame_prev != nullptr);
+    const GroupPlan gp = group_plan(g.k, f, older);
     d.complete = d.complete && gp.complete;      // a ring that does not move this frame: nobody writes its snapshot entry
     if (gp.nrounds == 0) continue;
     if ((hipStream_t)stream != c->atm_stream || !c->atm_stream) { int rc = atmos_wait_pending(c, stream); if (rc) return rc; }
-    if (c->ev_frame_prev) { if (gp.overlap) c->pipe.overlapped++; else c->pipe.behind++; }
-    ExtrudeRun run(c, st, g.b, g.n, stream);
+    if (older) { if (gp.overlap) c->pipe.overlapped++; else c->pipe.behind++; }
+    ExtrudeRun run(c, st, g.b, g.n, stream, true, origin_snap);
     run.overlap = gp.overlap; run.ride_ev = ride_ev;
     int rc = 0;
     if (gp.small) rc = run.launch(small_launch(g.k));
@@ -227,56 +225,27 @@ int aomarl_move_atmos(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accu
   int rc = check_range(c, st, b, n);
   if (rc) return rc;
   if (!accumx || !accumy) return fail("move_atmos: null accumulators");
-  if (c->premoved) {
-    rc = atmos_wait_pending(c, stream);
-    if (rc) return rc;
-    if (c->pre_screens == st->screens && c->pre_b == b && c->pre_n == n) {   // this frame's move is done
-      c->premoved = false;
-      return 0;
-    }
-  }
+  rc = atmos_wait_pending(c, stream);
+  if (rc) return rc;
+  if (c->order.take_move(st->screens, b, n)) return 0;      // this frame's move is done
   return move_atmos_now(c, st, b, n, accumx, accumy, stream, nullptr, nullptr);
 }
 
 static int prefetch_atmos_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accumx, float *accumy,
-                               void *stream, bool frame_marked) {
+                               void *stream, bool reuse_mark) {
   int rc = check_range(c, st, b, n);
   if (rc) return rc;
   if (!accumx || !accumy) return fail("prefetch_atmos: null accumulators");
-  if (c->premoved) return fail("prefetch_atmos: a prefetched frame is already pending");
+  if (c->order.move_pending()) return fail("prefetch_atmos: a prefetched frame is already pending");
   rc = side_stream(c);
   if (rc) return rc;
-  if (!frame_marked) {                           // readers of the screens are done
-    HIPCHK(hipEventRecord(c->ev_frame, (hipStream_t)stream));
-    c->ev_frame_cur = c->ev_frame;
-  }
-  // The stencil gather and the GEMM of the first round only READ the screens (like the frame kernel the
-  // caller has just launched): they need not wait for it.  The first kernel that writes a ring line
-  // does (ExtrudeRun::launch).  Only in the steady state, though: if the screens were last written on the
-  // caller's stream (reset, set_screen, an un-prefetched move), those writes are ordered before this
-  // point of that stream only, so the side stream waits for it right away.
-  c->side_joined = false;
-  if (c->capturing) {      // the side stream enters the capture at the fork recorded in front of the frame kernel
-    if (!c->fork_recorded) { HIPCHK(hipEventRecord(c->ev_fork, (hipStream_t)stream)); c->fork_recorded = true; }
-    HIPCHK(hipStreamWaitEvent(c->atm_stream, c->ev_fork, 0));
-  }
-  if (c->screens_dirty_main) {
-    HIPCHK(hipStreamWaitEvent(c->atm_stream, c->ev_frame_cur, 0));
-    c->frame_wait_pending = false;
-  } else {
-    c->frame_wait_pending = true;
-  }
+  HipOrderQueue q(__func__);
+  rc = c->order.prefetch_begin(q, stream, c->atm_stream, c->ev_frame, c->ev_fork, reuse_mark, c->capturing);
+  if (rc) return rc;
   MoveDone done = {true, false};
   rc = move_atmos_now(c, st, b, n, accumx, accumy, (void *)c->atm_stream, c->ev_moved, &done);
   if (rc) return rc;
-  if (c->frame_wait_pending) {            // nothing was extruded this frame: still order the marker behind the readers
-    HIPCHK(hipStreamWaitEvent(c->atm_stream, c->ev_frame_cur, 0));
-    c->frame_wait_pending = false;
-  }
-  c->screens_dirty_main = false;
-  if (!done.rode) HIPCHK(hipEventRecord(c->ev_moved, c->atm_stream));      // (else the move's one launch carried it)
-  c->premoved = true; c->pre_screens = st->screens; c->pre_b = b; c->pre_n = n;
-  return 0;
+  return c->order.prefetch_end(q, c->atm_stream, c->ev_moved, done.rode, st->screens, b, n);
 }
 
 int aomarl_prefetch_atmos(aomarl_ctx *c, aomarl_state *st, int b, int n, float *accumx, float *accumy,
@@ -362,19 +331,14 @@ static int reset_prologue(aomarl_ctx *c, aomarl_state *st, int b, int n, void *s
   if (n == 0) return 0;
   rc = atmos_wait_pending(c, stream);
   if (rc) return rc;
-  if (c->premoved && c->pre_screens == st->screens) {
-    // a prefetched frame is pending on these screens.  A reset of (at least) the prefetched range
-    // drops it -- the episode is over.  A reset of a part of it cannot: the other environments'
-    // screens and accumulators have already advanced, dropping the flag would make the next
-    // move_atmos advance them a second time (they would silently skip an atmosphere frame).
-    const bool covers = b <= c->pre_b && b + n >= c->pre_b + c->pre_n;
-    const bool disjoint = b + n <= c->pre_b || b >= c->pre_b + c->pre_n;
-    if (covers) c->premoved = false;
-    else if (!disjoint)
-      return fail("reset of environments [%d, %d) while the prefetched atmosphere frame of [%d, %d) is pending: "
-                  "reset the whole prefetched range, or call aomarl_move_atmos on it first",
-                  b, b + n, c->pre_b, c->pre_b + c->pre_n);
-  }
+  // a prefetched frame pending on these screens: a reset of (at least) the prefetched range drops it -- the episode
+  // is over.  A reset of a part of it cannot: the other environments' screens and accumulators have already
+  // advanced, dropping the flag would make the next move_atmos advance them a second time (they would silently skip
+  // an atmosphere frame).
+  if (c->order.reset_range(st->screens, b, n) == MOVE_OVERLAPS)
+    return fail("reset of environments [%d, %d) while the prefetched atmosphere frame of [%d, %d) is pending: "
+                "reset the whole prefetched range, or call aomarl_move_atmos on it first",
+                b, b + n, c->order.moved_b(), c->order.moved_b() + c->order.moved_n());
   return 0;
 }
 
@@ -385,7 +349,7 @@ int aomarl_reset(aomarl_ctx *c, aomarl_state *st, int b, int n, const uint32_t *
   if (n == 0) return 0;
   if (!seeds || !accumx || !accumy) return fail("reset: null argument");
   hipStream_t s = (hipStream_t)stream;
-  c->screens_dirty_main = true;
+  c->order.screens_written();
   rc = reset_small(c, st, b, n, seeds, accumx, accumy, c->seed_stage, c->seed_stage_n, s, true);
   if (rc) return rc;
   hipLaunchKernelGGL(k_fill_f32, dim3(2048), dim3(256), 0, s, st->screens + (size_t)b * c->sys.screen_stride,
@@ -567,7 +531,7 @@ int aomarl_reset_adopt(aomarl_ctx *c, aomarl_state *st, int b, int n, const uint
     if (rc) return rc;
   }
   hipStream_t s = (hipStream_t)stream;
-  c->screens_dirty_main = true;
+  c->order.screens_written();
   rc = reset_small(c, st, b, n, seeds, accumx, accumy, c->seed_stage, c->seed_stage_n, s, true);
   if (rc) return rc;
   HIPCHK(hipStreamWaitEvent(s, rp->ev, 0));
@@ -589,7 +553,7 @@ int aomarl_set_screen(aomarl_ctx *c, aomarl_state *st, int b, int n, int layer, 
   if (rc) return rc;
   if (layer < 0 || layer >= c->nlayers || !src) return fail("set_screen: bad argument");
   if (n == 0) return 0;
-  c->screens_dirty_main = true;
+  c->order.screens_written();
   hipLaunchKernelGGL(k_set_screen, dim3(256, n), dim3(256), 0, (hipStream_t)stream, c->sys, dev_state(st), b, layer, src);
   LAUNCHCHK();
   return 0;

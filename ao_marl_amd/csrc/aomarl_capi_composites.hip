@@ -104,8 +104,11 @@ static int frame_fused_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, int f
   rc = launch_frame_wave(fl, c->fw_variant);   // (aomarl_frame.hip; fw_variant: what it launched, aomarl_frame_kernel_name)
   if (rc) return rc;
   if (ev_mark) { HIPCHK(hipEventRecord(ev_mark, s)); ev_done = ev_mark; }
-  c->frame_marked = false;
   g_arith[hp ? AR_FRAME_SPLIT : AR_FRAME_F32]++;
+  HipOrderQueue q(__func__);
+  // (a pipelined frame, or the prefetch off: only "nothing marked the readers since"; no wait is issued)
+  rc = c->order.frame_launched(q, slot < 0 && c->prefetch_atmos, c->psf_stream, ev_done);
+  if (rc) return rc;
   if (slot >= 0) {
     c->pipe.ev_done_cur[slot] = ev_done;
     HIPCHK(hipStreamWaitEvent(c->psf_stream, ev_done, 0));
@@ -121,15 +124,10 @@ static int frame_fused_impl(aomarl_ctx *c, aomarl_state *st, int b, int n, int f
   if (c->prefetch_atmos) {
     // second axis of the PSF window: off the critical path (read by aomarl_comp_strehl at the end of
     // the step), so it goes to the side stream, in front of the next frame's extrusions
-    c->ev_frame_cur = ev_done; c->frame_marked = true;
-    c->side_joined = false;
-    HIPCHK(hipStreamWaitEvent(c->psf_stream, ev_done, 0));
     const FinishEvents ev = {nullptr, c->capturing ? nullptr : c->ev_psf};
     rc = launch_target_finish(FINISH_MFMA, c->sys, TR, TP, w.nblk, PEND, st->frame + b, n, c->psf_stream, &ev);
     if (rc) return rc;
-    if (c->capturing) HIPCHK(hipEventRecord(c->ev_psf, c->psf_stream));       // (a captured dispatch carries no events)
-    c->psf_side = true;
-    return 0;
+    return c->order.psf_finish_launched(q, c->capturing, c->ev_psf, c->psf_stream);
   }
   return launch_target_finish(FINISH_MFMA, c->sys, TR, TP, w.nblk, PEND, st->frame + b, n, s);
 }
@@ -153,14 +151,15 @@ static int next_part_one_sense(aomarl_ctx *c, aomarl_state *st, int b, int n, fl
     if (c->capturing && c->prefetch_atmos) {       // where the extrusion stream forks from the caller's
       rc = side_stream(c);
       if (rc) return rc;
-      HIPCHK(hipEventRecord(c->ev_fork, (hipStream_t)stream));
-      c->fork_recorded = true;
+      HipOrderQueue q(__func__);
+      rc = c->order.capture_fork(q, c->ev_fork, stream);
+      if (rc) return rc;
     }
     rc = aomarl_frame_fused(c, st, b, n, fl | (defer ? AOMARL_IMG_DM_FROM_VOLTAGE : 0), stream);
     if (rc) return rc;
-    if (c->prefetch_atmos && !c->premoved) {     // one frame ahead for ONE range at a time
+    if (c->prefetch_atmos && !c->order.move_pending()) {     // one frame ahead for ONE range at a time
       // nothing was launched on `stream` since the frame kernel: its mark stands for the screens' readers
-      rc = prefetch_atmos_impl(c, st, b, n, accumx, accumy, stream, c->frame_marked);
+      rc = prefetch_atmos_impl(c, st, b, n, accumx, accumy, stream, true);
       if (rc) return rc;
     }
     return 0;
@@ -174,7 +173,7 @@ static int next_part_one_sense(aomarl_ctx *c, aomarl_state *st, int b, int n, fl
   }
   rc = aomarl_comp_image(c, st, b, n, fl, stream);
   if (rc) return rc;
-  if (c->prefetch_atmos && !c->premoved) {
+  if (c->prefetch_atmos && !c->order.move_pending()) {
     rc = aomarl_prefetch_atmos(c, st, b, n, accumx, accumy, stream);
     if (rc) return rc;
   }

@@ -177,7 +177,7 @@ int aomarl_target_image(aomarl_ctx *c, aomarl_state *st, int b, int n, float *ou
   if (rc) return rc;
   if (!out) return fail("target_image: null output");
   if (n == 0) return 0;
-  if (c->premoved && c->pre_screens == st->screens)
+  if (c->order.move_pending_on(st->screens))
     return fail("target_image: the screens have already been moved to the next frame (aomarl_prefetch_atmos / "
                 "\"prefetch_atmos\"): the image of THIS frame cannot be formed any more -- run with the prefetch off");
   rc = atmos_wait_pending(c, stream);

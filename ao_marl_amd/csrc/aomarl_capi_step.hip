@@ -479,7 +479,7 @@ static int env_step_body(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, co
     if (rc) return rc;
     // the next frame's extrusions go beside centroids / control / agents, not beside the denoiser: that
     // kernel fills the GPU by itself and small kernels next to it only stretch both
-    if (c->prefetch_atmos && !c->premoved) {
+    if (c->prefetch_atmos && !c->order.move_pending()) {
       rc = aomarl_prefetch_atmos(c, st, 0, n, accumx, accumy, stream);
       if (rc) return rc;
     }
@@ -540,10 +540,11 @@ static int pipe_launch_frame(aomarl_ctx *c, aomarl_state *st, int q, void *strea
   auto &P = c->pipe;
   (void)stream;
   HIPCHK(hipStreamWaitEvent(P.fstream, P.ev_cmd, 0));       // recorded behind the kernel that wrote that parity's voltages / tip-tilt slot
-  if (!c->premoved || c->pre_screens != st->screens || c->pre_b != 0 || c->pre_n != st->nenv)
+  if (!c->order.move_is(st->screens, 0, st->nenv))
     return fail("frame pipeline: no prefetched atmosphere frame of the whole batch is pending");
-  HIPCHK(hipStreamWaitEvent(P.fstream, c->ev_moved, 0));
-  c->premoved = false;
+  HipOrderQueue oq(__func__);
+  int rc = c->order.frame_takes_move(oq, P.fstream, c->ev_moved);
+  if (rc) return rc;
   aomarl_state v = pipe_view(c, st, q);
   v.origin = P.snap[q];
   return frame_fused_impl(c, &v, 0, st->nenv, AOMARL_IMG_COG | AOMARL_IMG_NOISE | AOMARL_IMG_DM_FROM_VOLTAGE,
@@ -554,28 +555,20 @@ static int pipe_launch_frame(aomarl_ctx *c, aomarl_state *st, int q, void *strea
 // the group's plan allows (GroupPlan::overlap), behind the older one in any case; then the origins that frame will use
 static int pipe_prefetch(aomarl_ctx *c, aomarl_state *st, float *accumx, float *accumy, int older, int newest) {
   auto &P = c->pipe;
-  if (c->premoved) return fail("frame pipeline: a prefetched frame is already pending");
-  c->side_joined = false;
-  c->ev_frame_prev = P.ev_done_cur[older]; c->need_prev = true;
-  c->ev_frame_cur = P.ev_done_cur[newest]; c->frame_wait_pending = true;
+  if (c->order.move_pending()) return fail("frame pipeline: a prefetched frame is already pending");
+  c->order.pipe_prefetch_begin(P.ev_done_cur[older], P.ev_done_cur[newest]);
   // the kernels that advance the ring origins write them into that frame's snapshot as well (behind the same wait
   // as their ring writes); a copy of all origins only when some ring did not move at all
-  c->snap_target = P.snap[older];
   MoveDone done = {true, false};
-  int rc = move_atmos_now(c, st, 0, st->nenv, accumx, accumy, (void *)c->atm_stream, c->ev_moved, &done);
+  int rc = move_atmos_now(c, st, 0, st->nenv, accumx, accumy, (void *)c->atm_stream, c->ev_moved, &done, P.snap[older]);
   const bool complete = done.complete;
-  c->snap_target = nullptr;
-  if (!rc && !complete && c->need_prev && c->frame_wait_pending)   // nothing written yet: the copy overwrites what the older frame reads
-    rc = hipStreamWaitEvent(c->atm_stream, c->ev_frame_prev, 0) == hipSuccess ? 0 : fail("frame pipeline: hipStreamWaitEvent failed");
-  c->ev_frame_prev = nullptr; c->need_prev = false; c->frame_wait_pending = false;
+  HipOrderQueue q(__func__);
+  if (c->order.pipe_move_end(q, c->atm_stream, !rc && !complete)) rc = fail("frame pipeline: hipStreamWaitEvent failed");
   if (rc) return rc;
   if (!complete)
     HIPCHK(hipMemcpyAsync(P.snap[older], st->origin, sizeof(int32_t) * (size_t)st->nenv * c->nlayers * 2,
                           hipMemcpyDeviceToDevice, c->atm_stream));
-  c->screens_dirty_main = false;
-  if (!(done.rode && complete)) HIPCHK(hipEventRecord(c->ev_moved, c->atm_stream));     // (else the move's one launch carried it)
-  c->premoved = true; c->pre_screens = st->screens; c->pre_b = 0; c->pre_n = st->nenv;
-  return 0;
+  return c->order.prefetch_end(q, c->atm_stream, c->ev_moved, done.rode && complete, st->screens, 0, st->nenv);
 }
 
 static int env_step_pipelined(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const float *action, float gain,
@@ -588,13 +581,12 @@ static int env_step_pipelined(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *
     // ---- first step: the plain order, then the next frame ahead
     int rc = env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, f, plan, stream);
     if (rc) return rc;
-    if (!c->premoved || !c->psf_side) return 0;      // (the plain step did not leave the steady state behind: stay plain)
+    if (!c->order.steady_after_plain()) return 0;    // (the plain step did not leave the steady state behind: stay plain)
     rc = pipe_init(c, st);
     if (rc) return rc;
-    P.ev_done_cur[0] = c->ev_frame_cur;              // the plain frame used st's buffers: parity 0
     HIPCHK(hipEventRecord(P.ev_psf[0], c->psf_stream));
     P.psf_out[0] = true; P.psf_out[1] = false;
-    c->psf_side = false;
+    P.ev_done_cur[0] = (hipEvent_t)c->order.pipe_adopts_plain_frame();     // the plain frame used st's buffers: parity 0
     // v(t+1) = c(t), the newest entry of the delay line after its shift; tip-tilt shape from it
     aomarl_state v1 = pipe_view(c, st, 1);
     HIPCHK(hipMemcpyAsync(v1.voltage, st->com1, sizeof(float) * (size_t)n * st->ld_actu, hipMemcpyDeviceToDevice, s));
@@ -747,25 +739,17 @@ int aomarl_env_step(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const f
   // cheaply on this runtime, tools/graphbench.hip: 13 small kernels 29 us per replay against 37 us launched one by one)
   const bool pf = c->prefetch_atmos;
   const bool steady = stream && aomarl_frame_fused_available(c) && accumx && accumy &&
-                      (pf ? (c->premoved && c->pre_screens == st->screens && c->pre_b == 0 && c->pre_n == n) : !c->premoved) &&
+                      (pf ? c->order.move_is(st->screens, 0, n) : !c->order.move_pending()) &&
                       (!g->sel || (c->sel_checked == g->sel && c->sel_checked_n == g->dm_dim && c->sel_checked_nm == g->nmodes)) &&
                       g->nhist >= 0 && g->nhist <= 5 && g->ring_pos >= 0 && g->ring_pos <= g->nhist &&
                       move_uniform(nl, accumx, accumy, c->deltax, c->deltay, n, plan);
   if (!steady) return env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, f, sp, stream);
   hipStream_t s = (hipStream_t)stream;
-  int rc = 0;
-  if (pf) {
-    rc = side_stream(c);
-    if (rc) return rc;
-    if (!c->side_joined) {        // work issued on the side streams by plain calls: wait for it OUTSIDE the graph
-      HIPCHK(hipStreamWaitEvent(s, c->ev_moved, 0));
-      if (c->psf_side) HIPCHK(hipStreamWaitEvent(s, c->ev_psf, 0));
-      c->side_joined = true;
-    }
-  } else if (c->psf_side) {       // a PSF finish left on the side stream by an earlier call with the prefetch on
-    rc = psf_wait_pending(c, stream);
-    if (rc) return rc;
-  }
+  HipOrderQueue q(__func__);
+  int rc = pf ? side_stream(c) : 0;
+  // (without the prefetch: a PSF finish left on the side stream by an earlier call with the prefetch on)
+  if (!rc) rc = pf ? c->order.graph_join_outside(q, s, c->ev_moved, c->ev_psf) : c->order.psf_join(q, s, c->ev_psf);
+  if (rc) return rc;
   std::vector<long long> key;
   auto kp = [&](const void *p) { key.push_back((long long)(uintptr_t)p); };
   for (int l = 0; l < nl; l++) { key.push_back(plan.kx[l]); key.push_back(plan.ky[l]); }
@@ -792,12 +776,7 @@ int aomarl_env_step(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const f
       for (int l = 0; l < nl; l++) { c->frac_x[l] = mg.fx[l]; c->frac_y[l] = mg.fy[l]; }
     }
     g->ring_pos = (g->ring_pos + 1) % (g->nhist + 1);
-    if (pf) {
-      c->premoved = true; c->psf_side = true; c->side_joined = true;
-      c->frame_marked = true; c->frame_wait_pending = false; c->screens_dirty_main = false;
-    } else {
-      c->frame_marked = false; c->screens_dirty_main = true;
-    }
+    c->order.replayed(pf);
     for (int i = 0; i < AR_N; i++) g_arith[i] += hit->arith[i];
     memcpy(c->fw_variant, hit->fw_variant, sizeof(c->fw_variant));
     c->graph_hits++;
@@ -814,28 +793,23 @@ int aomarl_env_step(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const f
   // the body advances host bookkeeping while it is being RECORDED (no kernel runs): kept, so that a capture that
   // fails leaves the host where the device still is
   struct Snap {
-    std::vector<float> ax, ay; int ring_pos; bool premoved, psf_side, side_joined, frame_marked, frame_wait_pending, screens_dirty_main;
+    std::vector<float> ax, ay; int ring_pos; SideOrder order;
     float fx[AOMARL_MAX_LAYERS], fy[AOMARL_MAX_LAYERS];
   } snap;
   snap.ax.assign(accumx, accumx + (size_t)n * nl); snap.ay.assign(accumy, accumy + (size_t)n * nl);
-  snap.ring_pos = g->ring_pos; snap.premoved = c->premoved; snap.psf_side = c->psf_side; snap.side_joined = c->side_joined;
-  snap.frame_marked = c->frame_marked; snap.frame_wait_pending = c->frame_wait_pending; snap.screens_dirty_main = c->screens_dirty_main;
+  snap.ring_pos = g->ring_pos; snap.order = c->order;
   memcpy(snap.fx, c->frac_x, sizeof(snap.fx)); memcpy(snap.fy, c->frac_y, sizeof(snap.fy));
   auto restore = [&]() {
     memcpy(accumx, snap.ax.data(), sizeof(float) * snap.ax.size()); memcpy(accumy, snap.ay.data(), sizeof(float) * snap.ay.size());
-    g->ring_pos = snap.ring_pos; c->premoved = snap.premoved; c->psf_side = snap.psf_side; c->side_joined = snap.side_joined;
-    c->frame_marked = snap.frame_marked; c->frame_wait_pending = snap.frame_wait_pending; c->screens_dirty_main = snap.screens_dirty_main;
+    g->ring_pos = snap.ring_pos; c->order = snap.order;
     memcpy(c->frac_x, snap.fx, sizeof(snap.fx)); memcpy(c->frac_y, snap.fy, sizeof(snap.fy));
     for (int i = 0; i < AR_N; i++) g_arith[i] = before[i];
   };
   HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-  c->capturing = true; c->fork_recorded = false;
+  c->capturing = true; c->order.capture_begin();
   rc = env_step_body(c, st, g, action, gain, accumx, accumy, state_out, reward_out, f, sp, stream);
-  hipError_t je = hipSuccess;
-  if (!rc && pf) {                                          // the side streams join the caller's stream again
-    if (c->psf_side) je = hipStreamWaitEvent(s, c->ev_psf, 0);
-    if (je == hipSuccess && c->premoved) je = hipStreamWaitEvent(s, c->ev_moved, 0);
-  }
+  // the side streams join the caller's stream again (a failure is reported below, with the capture's)
+  const hipError_t je = !rc && pf && c->order.capture_join(q, s, c->ev_psf, c->ev_moved) ? q.err : hipSuccess;
   c->capturing = false;
   hipGraph_t graph = nullptr;
   const hipError_t ee = hipStreamEndCapture(s, &graph);
@@ -845,7 +819,6 @@ int aomarl_env_step(aomarl_ctx *c, aomarl_state *st, aomarl_env_glue *g, const f
     restore();
     return fail("env_step: graph capture failed: %s", hipGetErrorString(je != hipSuccess ? je : ee));
   }
-  if (pf) c->side_joined = true;
   aomarl_ctx::StepGraph sg;
   sg.key = key; sg.graph = graph; sg.exec = nullptr;
   for (int i = 0; i < AR_N; i++) sg.arith[i] = g_arith[i] - before[i];

@@ -752,6 +752,71 @@ def test_frame_pipeline_over_a_long_episode_with_ring_wraps():
 
 
 @pytest.mark.gpu
+def test_one_context_through_every_mode_gives_the_plain_steps():
+    """The other tests run each mode in an environment of its own; what one mode leaves behind for the next (which
+    waits are still owed, what is pending where: csrc/aomarl_order_host.h) shows only where they follow each other.  ONE
+    context: prefetched plain steps, aomarl_get_screen, a reset of half the prefetched range (refused, with its
+    text), the whole-range reset, steps with "graph_step" on (captures, then replays), "graph_step" off and the frame
+    pipeline on, a whole-range reset -- states, rewards, slopes and Strehl of every step bit for bit those of the same
+    steps in a context with the prefetch off and no pipeline."""
+    from ao_marl_amd.env import VecAoEnv
+    from ao_marl_amd.libaomarl import AomarlError
+    rl = dict(n_zernike_start_end=[0, 80], n_reverse_filtered_from_cmat=5)
+    nenv, nplain, ngraph, npipe = 4, 3, 10, 4
+    rng = np.random.default_rng(23)
+    out, actions = {}, None
+    for mode in ("mixed", "plain"):
+        mixed = mode == "mixed"
+        env = VecAoEnv("production_sh_10x10_2m", nenv, rl, initial_seed=41, seed_stride=16, n_agents_modal=1,
+                       prefetch_atmos=mixed, frame_pipeline=False)
+        sim = env.supervisor.sim
+        if actions is None:
+            actions = torch.from_numpy(rng.uniform(-1, 1, size=(nplain + ngraph + npipe, nenv, env.action_dim)).astype(np.float32)).cuda()
+        abuf = torch.empty_like(actions[0])                  # one address: a graph's key holds it
+        rec = []
+
+        def steps(t0, n):
+            for t in range(t0, t0 + n):
+                assert env._native_step_ok(False)
+                abuf.copy_(actions[t])
+                s, r, _, _ = env.step(abuf)
+                rec.extend([s.clone(), r.clone(), env.supervisor.get_slopes().clone(), env.supervisor.get_strehl().clone()])
+
+        with torch.cuda.stream(torch.cuda.Stream()):        # the null stream cannot be captured
+            rec.append(env.reset().clone())
+            steps(0, nplain)
+            assert sim.pending_atmos == mixed
+            assert torch.isfinite(sim.screen(0)).all()       # waits for the prefetched move, leaves it pending
+            if mixed:
+                with pytest.raises(AomarlError) as refusal:
+                    sim.reset([1, 2], env_begin=0, env_count=2)
+                assert ("reset of environments [0, 2) while the prefetched atmosphere frame of [0, 4) is pending: "
+                        "reset the whole prefetched range, or call aomarl_move_atmos on it first") in str(refusal.value)
+            rec.append(env.reset().clone())
+            if mixed:
+                sim.set_option("graph_step", 1)
+            steps(nplain, ngraph)
+            if mixed:
+                # the one wind of this configuration moves 2, 2, 2, 3 lines per frame and a graph's key holds that plan,
+                # the command ring's position (of 3) and the output ring's (of 6): from the seventh step on, every other
+                # step meets a graph again
+                cap, rep = sim.graph_stats()
+                assert cap >= 1 and rep >= 1 and cap + rep >= ngraph - 1, (cap, rep)
+                sim.set_option("graph_step", 0)
+                env.frame_pipeline = True
+            steps(nplain + ngraph, npipe)
+            assert sim.frame_pipeline_state()[0] == mixed    # a frame is in flight
+            rec.append(env.reset().clone())
+            assert not sim.frame_pipeline_state()[0]
+            torch.cuda.synchronize()
+        out[mode] = rec
+        del env
+    assert len(out["mixed"]) == len(out["plain"]) == 3 + 4 * (nplain + ngraph + npipe)
+    for k, (a, b) in enumerate(zip(out["mixed"], out["plain"])):
+        assert torch.equal(a, b), k
+
+
+@pytest.mark.gpu
 def test_small_chain_equals_the_general_chain_to_rounding():
     """Small systems: the control / agent chain of aomarl_env_step as two workgroup-per-environment kernels
     (k_small_head / k_small_tail, default) against the general chain of GEMMs and elementwise kernels ("small_chain" =
